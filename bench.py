@@ -1,9 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark: PCG + Jacobi iterations/s on the 5-point FDLaplacian2D, SpMV vs the HBM roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--side M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--side M] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, W warm-up iterations and the settle
+solve, ONE timed region of K iterations, the output dump when --dump-outputs is given, the JSON line
+(`value`, `ms_per_step`, and the roofline figures that come from the timed region's own events).
+--full adds everything else described below (5 timed regions with value = the median one, the
+extra keys, the 16384^2 series, the other configs, the CPU oracle), as the benchmark ran before the
+option existed. --dump-outputs DIR writes what the last timed psk_pcg call returned to its caller:
+DIR/x.npy (the solution vector; a fixed seeded sample of its entries when it is larger than
+DUMP_MAX_BYTES, the sampled indices in DIR/x_index.npy) and DIR/result.npy (iters, resid,
+resid_recursive, norm_b), all float64 (x_rank<r>.npy ... for rank r > 0 at N > 1). Every timed solve
+starts from x = 0 on inputs fixed by the arguments, so two builds can be compared entry for entry.
 
 One "step" = one PCG iteration (PCGSolver.py:109-138: SpMV, 2 dots + norm, 3 updates, Jacobi
 apply) over the whole matrix. The headline workload is the metric's own (BASELINE.json: "5-pt
@@ -176,8 +187,16 @@ def main():
     ap.add_argument("--scaling-side", type=int, default=16384,
                     help="also time configs[3]'s 16384^2 system at this N (the strong-scaling series; 0 = skip)")
     ap.add_argument("--scaling-steps", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps iterations each; value = the median (SURVEY.md §8d)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: 5 timed regions (value = the median), the "
+                         "extra keys, the strong-scaling series, the other configs, the CPU oracle (see --repeats, "
+                         "--scaling-side, --general, --config1/2/4, --gmres, --cpu-iters, which apply under --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed solve returned (x or a fixed seeded sample of it, and the result "
+                         "scalars) as float64 DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps iterations each; value = the median (SURVEY.md §8d); "
+                         "default 1, 5 under --full")
     ap.add_argument("--cpu-iters", type=int, default=50, help="timed oracle iterations for cpu_baseline (0 = skip)")
     ap.add_argument("--general", type=int, default=1,
                     help="also time the general-matrix path (double values, streamed DInv) on rank 0")
@@ -188,6 +207,8 @@ def main():
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "r6_pmc_traffic_%d.json"),
                     help="PMC traffic summary (tools/pmc_summary.py) of the same build; %%d = the side")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     LIVE.write("bench: start (pid %d, python %s)" % (os.getpid(), sys.version.split()[0]))
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -301,6 +322,9 @@ def main():
     regions = sys_.regions(args.steps, args.warmup, args.repeats, barrier, dist)
     imed = sorted(range(len(regions)), key=lambda i: regions[i][0])[len(regions) // 2]
     dt, spmv_ms_med, spmv_launches = regions[imed]
+    if args.dump_outputs:
+        progress("dump outputs")
+        dump_outputs(N, sys_, args.dump_outputs, rank)
 
     out = None
     if rank == 0:
@@ -322,6 +346,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "settle": {"iters": sys_.settle_iters(), "note": "one untimed solve (~0.3 s; same count on every rank) after "
                                                              "the warm-up iterations, right before the first timed region"},
             "ms_per_step": dt * 1e3 / args.steps,
@@ -340,7 +365,7 @@ def main():
                                      else ("rccl allgather" if transport == "rccl" else "host-shm allgather"),
                                      "dots_note": dots_note}
                        if world > 1 else None},
-            "repeats": {"regions": len(regions), "value_is": "median region",
+            "repeats": {"regions": len(regions), "value_is": "median region" if len(regions) > 1 else "the one timed region",
                         "it_s": [args.steps / r[0] for r in regions],
                         "spmv_avg_launch_ms": [r[1] for r in regions]},
             "roofline": {"bound": "hbm", "kernel": pmc.pop("kernel", None) or spmv_kernel_label(lay, 1),
@@ -364,7 +389,7 @@ def main():
                                        "frac_of_aggregate_peak": biter * it_s / 1e9 / (HBM_PEAK_GBPS * world)},
             "setup_s": sys_.setup_s,
         }
-        if world == 1:
+        if world == 1 and args.full:
             # what the sampled per-launch HIP events of the timed regions cost: the same regions without them
             ne = sys_.regions(args.steps, 0, 3, barrier, dist, events=False)
             out["regions_without_kernel_events"] = {"it_s": [args.steps / r[0] for r in ne],
@@ -392,7 +417,7 @@ def main():
     sys_.free()
 
     # ---- configs[3]'s 16384^2 system at the same N: the strong-scaling series of the >= 6x target ----
-    if args.scaling_side and args.scaling_side != m:
+    if args.full and args.scaling_side and args.scaling_side != m:
         ms_ = args.scaling_side
         progress("strong_scaling_%d" % ms_)
         big = PcgSystem(N, ms_, comm if world > 1 else None, world)
@@ -419,19 +444,20 @@ def main():
         big.free()
 
     if rank == 0:
-        if world == 1 and args.config1 and m != 4096:
+        extras = world == 1 and args.full
+        if extras and args.config1 and m != 4096:
             progress("configs1_pcg_jacobi_4096")
             out["configs1_pcg_jacobi_4096"] = pcg_4096(N)
-        if world == 1 and args.gmres:
+        if extras and args.gmres:
             progress("gmres30_jacobi_4096")
             out["gmres30_jacobi_4096"] = gmres_arnoldi(N)
-        if world == 1 and args.config2:
+        if extras and args.config2:
             progress("configs2_gmres30_ilut (host SuperLU ILUT first)", "host")
             out["configs2_gmres30_ilut"] = gmres_ilut(N)
-        if world == 1 and args.config4:
+        if extras and args.config4:
             progress("configs4_pcg_amg_8192 (host SA setup first)", "host")
             out["configs4_pcg_amg_8192"] = pcg_amg(N)
-        if world == 1 and args.cpu_iters > 0:
+        if extras and args.cpu_iters > 0:
             progress("cpu_baseline", "host")
             out["cpu_baseline"] = cpu_baseline(m, args.cpu_iters)
         else:
@@ -442,6 +468,31 @@ def main():
         barrier()
         N.lib.psk_comm_destroy(comm)
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 32 << 20       # a larger x is written as DUMP_SAMPLE of its entries (with their indices)
+DUMP_SAMPLE = 1 << 20
+DUMP_SEED = 20240607
+
+
+def dump_outputs(N, sys_, dirpath, rank):
+    """What the last timed psk_pcg call handed back to its caller, as float64 .npy files: this rank's rows of
+    the solution x (all of them up to DUMP_MAX_BYTES; above that the entries at DUMP_SAMPLE sorted indices drawn
+    without replacement by default_rng(DUMP_SEED), a function of the row count alone, and those indices) and
+    the result scalars. Runs after the timed regions and before any other solve overwrites x."""
+    os.makedirs(dirpath, exist_ok=True)
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    x = np.empty(sys_.nloc, dtype=np.float64)
+    N.check(N.lib.psk_synchronize(), "sync")
+    N.check(N.lib.psk_d2h(N.ptr(x), sys_.dsol, sys_.nloc * 8), "d2h")
+    if x.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(sys_.nloc, size=DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(dirpath, "x_index%s.npy" % suffix), idx.astype(np.float64))
+        x = x[idx]
+    np.save(os.path.join(dirpath, "x%s.npy" % suffix), x)
+    r = sys_.last
+    np.save(os.path.join(dirpath, "result%s.npy" % suffix),
+            np.array([r.iters, r.resid, r.resid_recursive, r.norm_b], dtype=np.float64))
 
 
 def comm_breakdown(comm, t_iter_s, spmv_ms, world):
@@ -628,6 +679,7 @@ class PcgSystem:
             dt = time.perf_counter() - t0
             LIVE.tick("timed region")
             assert res.iters == steps and res.success == 1, (res.iters, res.success)
+            self.last = res   # the last timed solve's result struct (its x is in dsol): what --dump-outputs writes
             spmv_ms, gat, halo = res.spmv_ms, res.gather_ms, res.halo_ms
             if dist is not None:
                 import torch

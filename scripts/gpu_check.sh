@@ -10,10 +10,10 @@ ok() { local c=$1; [ $c -eq 0 ] || [ $c -eq 1 ]; }   # 0 pass, 1 test/bench fail
 sha256sum pysolvers_amd/_lib/libpsk.so > $OUT/${TAG}_lib.sha256
 timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 400 --timeout-method thread > $OUT/${TAG}_pytest.log 2>&1
 c=$?; echo "pytest exit $c"; tail -3 $OUT/${TAG}_pytest.log; ok $c || exit $c
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 c=$?; echo "bench exit $c"; ok $c || exit $c
 PSK_DUMP_MAPS=$OUT/${TAG}_maps.txt timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof -o run --output-format csv -- \
-    python -u bench.py --steps 20 --warmup 2 --cpu-iters 0 --general 0 --config1 0 --gmres 0 --scaling-side 0 \
+    python -u bench.py --full --steps 20 --warmup 2 --cpu-iters 0 --general 0 --config1 0 --gmres 0 --scaling-side 0 \
     > $OUT/${TAG}_prof.json 2> $OUT/${TAG}_prof.err
 echo "profiled exit $?"
 python tools/trace_stats.py $(find $OUT/${TAG}_prof -name "*kernel_trace.csv" | head -1) > $OUT/${TAG}_trace_stats.csv

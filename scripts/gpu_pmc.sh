@@ -14,7 +14,7 @@ for S in ${SIDES:-16384 3163}; do
   for C in FETCH_SIZE WRITE_SIZE; do
     echo "== pmc side $S $C"
     timeout -s KILL 300 rocprofv3 --pmc $C --kernel-trace -d $OUT/pmc_${TAG}_${S}_$C -o run --output-format csv -- \
-        python bench.py --side $S $ARGS > $OUT/pmc_${TAG}_${S}_$C.json 2> $OUT/pmc_${TAG}_${S}_$C.err
+        python bench.py --full --side $S $ARGS > $OUT/pmc_${TAG}_${S}_$C.json 2> $OUT/pmc_${TAG}_${S}_$C.err
     rc=$?; [ $rc -ne 0 ] && { echo "pmc $S $C exit $rc"; tail -5 $OUT/pmc_${TAG}_${S}_$C.err; exit $rc; }
   done
 done

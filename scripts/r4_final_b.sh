@@ -8,7 +8,7 @@ OUT=gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 TAG=${1:-r4g}
 sha256sum pysolvers_amd/_lib/libpsk.so > $OUT/${TAG}_lib.sha256
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof -o run --output-format csv -- \
-    python -u bench.py --steps 20 --warmup 5 --cpu-iters 0 > $OUT/${TAG}_prof.json 2> $OUT/${TAG}_prof.err
+    python -u bench.py --full --steps 20 --warmup 5 --cpu-iters 0 > $OUT/${TAG}_prof.json 2> $OUT/${TAG}_prof.err
 c=$?; echo "profiled bench exit $c"
 python tools/trace_stats.py $(find $OUT/${TAG}_prof -name "*kernel_trace.csv" | head -1) > $OUT/${TAG}_trace_stats.csv
 # the headline regions' own SpMV launches (the bench line's roofline.avg_launch_ms samples every 8th of them)

@@ -17,7 +17,7 @@ c=$?; echo "pytest exit $c"; tail -3 $OUT/${TAG}_pytest.log; ok $c || exit $c
 timeout -k 10 300 python -u tools/fixed_cost.py > $OUT/${TAG}_fixed.json 2> $OUT/${TAG}_fixed.err
 c=$?; echo "fixed exit $c"; cat $OUT/${TAG}_fixed.json; ok $c || exit $c
 for v in 1 0 1 0; do
-  PSK_SPMV_DIAG=$v timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --cpu-iters 0 --general 0 --config1 0 --gmres 0 --config2 0 --config4 0 > $OUT/${TAG}_bench_diag$v.json 2> $OUT/${TAG}_bench_diag$v.err
+  PSK_SPMV_DIAG=$v timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --cpu-iters 0 --general 0 --config1 0 --gmres 0 --config2 0 --config4 0 > $OUT/${TAG}_bench_diag$v.json 2> $OUT/${TAG}_bench_diag$v.err
   c=$?; echo "bench diag=$v exit $c"; ok $c || exit $c
   python -c "import json,sys; d=json.load(open('$OUT/${TAG}_bench_diag$v.json')); r=d['roofline']; print('diag=$v', round(d['value'],1), r['avg_launch_ms'], round(r['frac'],3), d['roofline']['layout'], d.get('strong_scaling_16384',{}).get('pcg_it_per_s'), d['fixed_overhead']['fixed_overhead_ms'], d['spmv_plain_batch50']['avg_launch_ms'])"
 done

@@ -11,6 +11,6 @@ c=$?; echo "ab exit $c"; python tools/ab_summary.py $OUT/${TAG}_ab.jsonl; [ $c -
 timeout -k 10 700 python -u -m pytest tests/test_gpu_amg.py tests/test_gpu_parity.py tests/test_gpu_progress.py tests/test_abi.py tests/test_gpu_multirank.py -x -q --timeout 300 --timeout-method thread > $OUT/${TAG}_pytest.log 2>&1
 c=$?; echo "pytest exit $c"; tail -5 $OUT/${TAG}_pytest.log; [ $c -le 1 ] || exit $c
 PSK_BENCH_TRANSPORT=host timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 20 --warmup 5 > $OUT/${TAG}_rehearsal_n2.json 2> $OUT/${TAG}_rehearsal_n2.err
+    --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 20 --warmup 5 > $OUT/${TAG}_rehearsal_n2.json 2> $OUT/${TAG}_rehearsal_n2.err
 c=$?; echo "rehearsal exit $c"; tail -4 $OUT/${TAG}_rehearsal_n2.err
 exit $c
