@@ -30,6 +30,9 @@
  *   psk_prec_create_amg  AMGPreconditioner.apply (AMGPreconditioner.py:46-51) ->
  *                    AMGVCycleSolver.solve (VCycleSolver.py:52-95) -> VCycleManager.runLevel
  *                    (VCycleManager.py:31-62), hierarchy built on the host.
+ *   psk_vcycle       AMGVCycleSolver.solve as a solver of its own (VCycleSolver.py:52-95): the
+ *                    cycles of a psk_prec_create_amg hierarchy with the loop, the stopping test and
+ *                    the history on the device.
  *   psk_mm_*         scipy.io.mmread(path).tocsr() (examples/DHTestProblem.py:27-28).
  *   psk_sa_aggregate BuildAggregates + BuildFilteredMatrix (SmoothedAggregation.py:57-183),
  *                    O(nnz) host code.
@@ -314,6 +317,19 @@ int psk_pcg(const psk_csr *A, const psk_prec *M, const double *b, double *x, con
             psk_result *res, double *hist, int32_t loc);
 int psk_gmres(const psk_csr *A, const psk_prec *M, const double *b, double *x, const psk_ctl *ctl,
               psk_result *res, double *hist, int32_t loc);
+/* The standalone AMG V-cycle solver, AMGVCycleSolver.solve (VCycleSolver.py:52-95), on the device: M is a
+ * PSK_PREC_AMG whose finest level matrix is the system matrix (PSK_ERR_ARG otherwise); its own num_iters and
+ * tau are ignored, ctl->maxiter (> 0) and ctl->tau rule. x0 = copy(b) (:69), or the caller's x with
+ * PSK_VCYCLE_X0_GIVEN. Each cycle: x = runCycle(b, x), r = b - A x, hist[k] = ||r||, stop when
+ * ||r|| < tau*||b|| (strict, :90): PSK_CONVERGED, iters = k+1, exit = PSK_EXIT_TOLERANCE, x = that cycle's
+ * iterate. maxiter reached: handleMaxiter(maxiter-1, ...) — PSK_MAXITER, iters = maxiter-1, success =
+ * !fail_on_maxiter, x = the last iterate, resid = the last norm, exit = PSK_EXIT_MAXITER. b = 0: x = 0,
+ * iters = 1, exit = PSK_EXIT_NONE, no cycle runs. ctl->check_every: cycles between the host's looks at the
+ * device's done word (0 = 1); the results do not depend on it. ctl's time_kernels, restart and norm_b are
+ * ignored; res->spmv_ms, gather_ms, halo_ms and comm_samples are 0. */
+#define PSK_VCYCLE_X0_GIVEN 1   /* x holds the starting iterate; default x0 = copy(b), VCycleSolver.py:69 */
+int psk_vcycle(const psk_prec *M, const double *b, double *x, const psk_ctl *ctl,
+               psk_result *res, double *hist, int32_t flags, int32_t loc);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ------------------------------------- */
 #define PSK_UNIQUE_ID_BYTES 128

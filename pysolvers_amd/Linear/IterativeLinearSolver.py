@@ -79,6 +79,22 @@ class IterativeLinearSolver(LinearSolver, IterativeSolver):
         self._dA, self._dA_src = dA, A
         return dA
 
+    @staticmethod
+    def _solve_vectors(b, n):
+        """(x, loc, b) for a solver entry point: an output vector of b's kind (DeviceVector, CUDA float64 tensor
+        or host ndarray), where the two live, and b as the library takes it."""
+        if isinstance(b, DeviceVector):
+            return DeviceVector(n), N.PSK_DEVICE, b
+        if is_device_vector(b):
+            import torch
+            if b.dtype != torch.float64 or not b.is_contiguous():
+                raise TypeError("device right-hand side must be a contiguous float64 tensor")
+            x = torch.empty_like(b)
+            torch_stream_ready(b, x)
+            return x, N.PSK_DEVICE, b
+        bp = np.ascontiguousarray(b, dtype=np.float64)
+        return np.empty_like(bp), N.PSK_HOST, bp
+
     def _device_solve(self, A, b):
         n, nc = A.shape
         if not (isinstance(A, DeviceCSR) and A.comm is not None):
@@ -119,17 +135,7 @@ class IterativeLinearSolver(LinearSolver, IterativeSolver):
                        norm_b=normb_caller)
         res = N.PskResult()
         hist = np.zeros(max(maxiter, 1), dtype=np.float64)
-        if isinstance(b, DeviceVector):
-            x, loc, bp = DeviceVector(n), N.PSK_DEVICE, b
-        elif is_device_vector(b):
-            import torch
-            if b.dtype != torch.float64 or not b.is_contiguous():
-                raise TypeError("device right-hand side must be a contiguous float64 tensor")
-            x, loc, bp = torch.empty_like(b), N.PSK_DEVICE, b
-            torch_stream_ready(b, x)
-        else:
-            bp = np.ascontiguousarray(b, dtype=np.float64)
-            x, loc = np.empty_like(bp), N.PSK_HOST
+        x, loc, bp = self._solve_vectors(b, n)
         fn = getattr(N.lib, self._entry)
         N.check(fn(dA.handle, ph, N.ptr(bp), N.ptr(x), ctypes.byref(ctl), ctypes.byref(res), N.ptr(hist), loc),
                 self._entry)

@@ -18,3 +18,4 @@ from .PreconditionerType import (IdentityPreconditionerType, Jacobi, JacobiPreco
                                  PreconditionerType)
 from .SmoothedAggregation import SA_coarsen, SmoothedAggregationMLHierarchy
 from .TriangularSolve import TriangularSolveChain
+from .VCycleSolver import AMGVCycle, AMGVCycleSolver

@@ -19,6 +19,7 @@ ABI_VERSION = 4          # include/psk.h PSK_ABI_VERSION (psk_ctl.norm_b in 2, p
 PSK_CONVERGED, PSK_MAXITER, PSK_BREAKDOWN, PSK_TRUE_RESID_FAIL = 0, 1, 2, 3
 PSK_EXIT_NONE, PSK_EXIT_TOLERANCE, PSK_EXIT_ARNOLDI_BREAKDOWN, PSK_EXIT_MAXITER, PSK_EXIT_DOT_BREAKDOWN = 0, 1, 2, 3, 4
 PSK_HOST, PSK_DEVICE = 0, 1
+PSK_VCYCLE_X0_GIVEN = 1   # psk_vcycle flags: x holds the starting iterate
 PSK_PREC_IDENTITY, PSK_PREC_JACOBI, PSK_PREC_ILU, PSK_PREC_AMG, PSK_PREC_DENSE = 0, 1, 2, 3, 4
 PSK_LAYOUT_CSR, PSK_LAYOUT_SLICED, PSK_LAYOUT_SLICED_WIDE, PSK_LAYOUT_SLICED_DICT, PSK_LAYOUT_DIAG = 0, 1, 2, 3, 4
 PSK_UNIQUE_ID_BYTES = 128
@@ -90,6 +91,7 @@ SIGNATURES = {
     "psk_sa_aggregate": (ctypes.c_int, [I64, P, P, P, F64, P, ctypes.POINTER(I64), P]),
     "psk_pcg": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_gmres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
+    "psk_vcycle": (ctypes.c_int, [P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32, I32]),
     "psk_comm_unique_id": (ctypes.c_int, [P]),
     "psk_comm_init": (ctypes.c_int, [I32, I32, P, PP]),
     "psk_comm_destroy": (ctypes.c_int, [P]),

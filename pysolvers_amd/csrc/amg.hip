@@ -46,6 +46,7 @@ struct AmgHierarchy {
     std::vector<DevBuf> x, f, r, t;   // per level (f unused on the finest level: f = v)
     DevBuf scal;                      // [0] = ||v||^2, [1] = flag (as int64), partials after
     std::vector<GsPairLevel> gp;      // per level
+    DevBuf loop;                      // the standalone solver's device words (vcycle.hip), grow-only
 };
 
 void amg_free(AmgHierarchy *h) {
@@ -56,6 +57,7 @@ void amg_free(AmgHierarchy *h) {
     for (auto &b : h->t) b.release();
     for (auto &g : h->gp) g.pub.release();
     h->scal.release();
+    h->loop.release();
     delete h;
 }
 
@@ -770,27 +772,67 @@ static int amg_level(const AmgHierarchy *h, const Context *c, int lev, const dou
     return amg_smooth(h, c, lev, f, x, h->nu_post, s);                            // :59
 }
 
+// ---- what amg_apply and the standalone solver (vcycle.hip, psk_vcycle) share: the loop's vectors and scalars on the
+// finest level, its start, one cycle and the residual with its in-launch sum
+int amg_loop_view(const psk_prec *M, AmgLoop *out) {
+    if (!M || M->kind != PSK_PREC_AMG || !M->amg) return fail(PSK_ERR_ARG, "amg_loop_view: not an AMG preconditioner");
+    AmgHierarchy *h = M->amg;
+    const int top = h->L - 1;
+    out->A = h->A[top];
+    out->x = h->x[top].as<double>();
+    out->r = h->r[top].as<double>();
+    out->normb2 = h->scal.as<double>();
+    out->sum = h->scal.as<double>() + 2;
+    out->work = &h->loop;
+    return PSK_OK;
+}
+
+// scal[0] = ||v||^2, flag = 0, x = copy(v) (VCycleSolver.py:63, :69)
+int amg_loop_start(const psk_prec *M, const Context *c, const double *v, hipStream_t s) {
+    const AmgHierarchy *h = M->amg;
+    const int64_t n = M->n;
+    double *x = h->x[h->L - 1].as<double>();
+    double *scal = h->scal.as<double>();
+    int64_t *flag = reinterpret_cast<int64_t *>(scal + 1);
+    double *part = scal + 2;
+    const int gv = grid_for_rows(c, n, kVecTile);
+    hipLaunchKernelGGL(amg_sqnorm_partial_kernel, dim3(gv), dim3(kBlock), 0, s, n, v, part, x);   // + x = copy(b) (:69)
+    PSK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(amg_init_kernel, dim3(1), dim3(kBlock), 0, s, part, gv, scal, flag);
+    PSK_HIP(hipGetLastError());
+    return PSK_OK;
+}
+
+// x = runCycle(v, x) on the finest level's x (VCycleSolver.py:81)
+int amg_cycle(const psk_prec *M, const Context *c, const double *v, hipStream_t s) {
+    const AmgHierarchy *h = M->amg;
+    return amg_level(h, c, h->L - 1, v, h->x[h->L - 1].as<double>(), s);
+}
+
+// r = v - A x with ||r||^2 finished in the same launch, into scal[2] (VCycleSolver.py:84, :87)
+int amg_residual(const psk_prec *M, const double *v, hipStream_t s) {
+    const AmgHierarchy *h = M->amg;
+    const int top = h->L - 1;
+    return launch_spmv(h->A[top], kSpmvResid, h->x[top].as<double>(), h->r[top].as<double>(), nullptr, v,
+                       h->scal.as<double>() + 2, nullptr, s);
+}
+
 int amg_apply(const psk_prec *M, const double *v, double *out, hipStream_t s) {
     const AmgHierarchy *h = M->amg;
     const int64_t n = M->n;
     if (n == 0) return PSK_OK;
     Context *c;
     PSK_TRY(ctx(&c));
-    const int top = h->L - 1;
-    psk_csr *A = h->A[top];
-    double *x = h->x[top].as<double>(), *r = h->r[top].as<double>();
+    double *x = h->x[h->L - 1].as<double>();
     double *scal = h->scal.as<double>();
     int64_t *flag = reinterpret_cast<int64_t *>(scal + 1);
     double *part = scal + 2;
-    const int gv = grid_for_rows(c, n, kVecTile), ga = 1;   // the residual SpMV's sum: in-launch
-    hipLaunchKernelGGL(amg_sqnorm_partial_kernel, dim3(gv), dim3(kBlock), 0, s, n, v, part, x);   // + x = copy(b) (:69)
-    PSK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(amg_init_kernel, dim3(1), dim3(kBlock), 0, s, part, gv, scal, flag);
-    PSK_HIP(hipGetLastError());
+    const int ga = 1;   // the residual SpMV's sum: in-launch
+    PSK_TRY(amg_loop_start(M, c, v, s));
     for (int k = 0; k < h->num_iters; ++k) {
-        PSK_TRY(amg_level(h, c, top, v, x, s));                                            // runCycle (:79)
+        PSK_TRY(amg_cycle(M, c, v, s));                                                    // runCycle (:79)
         if (k + 1 < h->num_iters) {
-            PSK_TRY(launch_spmv(A, kSpmvResid, x, r, nullptr, v, part, nullptr, s));   // r = b - A x (:82)
+            PSK_TRY(amg_residual(M, v, s));                                                // r = b - A x (:82)
             hipLaunchKernelGGL(amg_check_kernel, dim3(1), dim3(kBlock), 0, s, part, ga, scal, h->tau, flag);
             PSK_HIP(hipGetLastError());
             hipLaunchKernelGGL(amg_copy_if_kernel, vgrid(n), dim3(kBlock), 0, s, n, flag, (int64_t)1, x, out);

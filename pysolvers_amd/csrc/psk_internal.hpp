@@ -945,6 +945,17 @@ int amg_gs_pair(psk_prec *M, int set, int *on, int *eligible);   // x += M^-1 v
 int ilu_check_error(const psk_prec *M, hipStream_t s);
 int amg_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);
 void amg_free(AmgHierarchy *h);
+// the V-cycle loop's pieces, shared by amg_apply and psk_vcycle (vcycle.hip): the finest level's matrix, iterate
+// and residual, ||b||^2 (normb2[0]), the residual SpMV's sum (sum[0]) and the solver's own grow-only device words
+struct AmgLoop {
+    psk_csr *A;
+    double *x, *r, *normb2, *sum;
+    DevBuf *work;
+};
+int amg_loop_view(const psk_prec *M, AmgLoop *out);
+int amg_loop_start(const psk_prec *M, const Context *c, const double *v, hipStream_t s);   // ||v||^2, x = copy(v)
+int amg_cycle(const psk_prec *M, const Context *c, const double *v, hipStream_t s);        // x = runCycle(v, x)
+int amg_residual(const psk_prec *M, const double *v, hipStream_t s);                       // r = v - A x, ||r||^2
 int dense_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);
 int dense_check_error(const psk_prec *M, hipStream_t s);
 void dense_free(DenseInverse *d);
