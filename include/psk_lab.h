@@ -28,6 +28,15 @@ int psk_lab_dispatch_probe(int32_t nwg, int32_t lds_bytes, double usec, int64_t 
 /* Lab: occupiers per XCD (HW_REG_XCC_ID) of the last psk_lab_occupy_begin, counts[8]. */
 int psk_lab_occupy_xcc(int32_t *counts);
 int psk_lab_trisolve_workers(const psk_prec *M, int32_t which, int32_t *enrolled, int32_t *grid);
+/* Lab / tests of the triangular-solve planner (plan_factor, trisolve_plan.hip); touches no GPU. The plan of one
+ * factor (CSR with its diagonal unless `unit`; nat: the natural index of every row, or NULL) for a device of
+ * num_cus CUs whose sync-free launch runs syncfree_waves waves (on a device: psk_lab_trisolve_workers' grid x 4):
+ * *schedule = the TriSchedule chosen, est[6] = the cost models' estimates in us by TriSchedule (-1: not
+ * eligible), info[8] = levels, band K / blocks / ring words / narrow, grid K / dictionary records, levels steps
+ * (0 where the layout was not built). Reads PSK_TRISOLVE_* / PSK_BAND_NARROW as factor creation does. */
+int psk_lab_trisolve_plan(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, int32_t upper,
+                          int32_t unit, const int32_t *nat, int32_t num_cus, int64_t syncfree_waves, int32_t *schedule,
+                          double *est, int64_t *info);
 /* Lab / tests of the AMG smoother's paired Gauss-Seidel sweeps (round 6, amg.hip gs_pair_kernel): set = 0 runs
  * every level's sweeps one launch each (the serialized path), 1 pairs them on the levels that qualify, -1
  * leaves the setting; *levels_on = the levels pairing now, *levels_eligible = the levels that qualify. */

@@ -36,7 +36,7 @@ class TriangularSolveChain(DeviceOperator, GenericPreconditioner):
 
     L: lower-triangular CSR (or None), U: upper-triangular CSR (or None); *_unit: unit diagonal
     (stored diagonal entries ignored), else the stored diagonal divides. Rows of each factor are
-    solved by one wave each, in a host-computed dependency-level order (see pysolvers_amd/csrc/ilu.hip).
+    solved by one wave each, in a host-computed dependency-level order (see pysolvers_amd/csrc/trisolve.hip).
     """
 
     device_kind = N.PSK_PREC_ILU

@@ -99,7 +99,7 @@ static_assert(kGpLds <= 160 * 1024, "one workgroup's LDS");
 // five waves of a workgroup share four SIMDs; wave w runs on SIMD w % 4)
 constexpr int kGpW1st = 1, kGpWRes = 2, kGpW2nd = 3, kGpWStream = 4;
 constexpr uint32_t kGpOOB = 0xFFFFFFFFu;   // a buffer offset out of range: loads 0, drops the store
-constexpr uint64_t kGpSentinel = 0x7FF4DEAD0000BEEFull;   // ilu.hip's sentinel: an sNaN payload
+constexpr uint64_t kGpSentinel = 0x7FF4DEAD0000BEEFull;   // trisolve.hpp's sentinel: an sNaN payload
 constexpr int64_t kGpMaxSpins = 1ll << 22, kGpDone = INT64_MAX / 4;
 
 struct GsPairArgs {
@@ -143,7 +143,7 @@ __device__ __forceinline__ bool gp_wait(const int64_t *c, int64_t want, int32_t 
     return true;
 }
 // buffer (bounds-checked) loads and stores: every lane issues every one of them with no branch around it, so
-// the compiler's vmcnt waits count exactly the operations in flight (ilu.hip, the grid kernel's note)
+// the compiler's vmcnt waits count exactly the operations in flight (trisolve.hpp, the grid kernel's buffer-access note)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t gp_rsrc(const double *p, int64_t n) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(p), (short)0, (int)(uint32_t)(n * 8), 0x00020000);
 }
@@ -173,7 +173,7 @@ __device__ __forceinline__ double gp_shl1(double v) {
 }
 // U's off-diagonal sum of one row as the serialized schedule forms it: LANES = false, the grid / band / levels
 // kernels' fma chain over the stored order from 0.0; LANES = true, the sync-free / LDS / partitioned kernels'
-// lane partials (entry k's product in lane k, fma(v, x, 0.0)) added by the wave reduction (ilu.hip row_total:
+// lane partials (entry k's product in lane k, fma(v, x, 0.0)) added by the wave reduction (trisolve.hpp row_total:
 // with two entries the one sum p0 + p1, the other lanes' zeros adding exactly nothing). An absent entry comes
 // with coefficient 0: fma(0, v, acc) = acc for a finite v and an acc that is not -0 (acc starts at +0, and an
 // fma onto +0 never rounds to -0), exactly the grid kernel's padding entries; the selects stay off the chain.

@@ -3,7 +3,7 @@
 // CUs while a solve runs (the forward-progress tests, tests/test_gpu_progress.py), a dispatch probe and the
 // enrolment count of the last sync-free triangular-solve launch. Declared in include/psk_lab.h; nothing in the
 // product path calls them.
-#include "psk_internal.hpp"
+#include "trisolve.hpp"
 #include "../../include/psk_lab.h"
 
 #include <chrono>
@@ -155,6 +155,25 @@ extern "C" int psk_lab_trisolve_workers(const psk_prec *M, int32_t which, int32_
     PSK_HIP(hipMemcpy(&v, T.sched + kSchedLast, sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (enrolled) *enrolled = (int32_t)v;
     if (grid) *grid = syncfree_grid(c);
+    return PSK_OK;
+}
+
+// the host planner's view of one factor (no GPU, no Context)
+extern "C" int psk_lab_trisolve_plan(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals,
+                                     int32_t upper, int32_t unit, const int32_t *nat, int32_t num_cus,
+                                     int64_t syncfree_waves, int32_t *schedule, double *est, int64_t *info) {
+    using namespace psk;
+    if (n < 0 || !rowptr || (rowptr[n] > 0 && (!colidx || !vals)) || num_cus < 1 || syncfree_waves < 1 || !schedule || !est || !info)
+        return fail(PSK_ERR_ARG, "psk_lab_trisolve_plan: bad arguments");
+    FactorPlan P;
+    PSK_TRY(plan_factor(n, rowptr, colidx, vals, upper != 0, unit != 0,
+                        nat ? std::vector<int32_t>(nat, nat + n) : std::vector<int32_t>(), num_cus, syncfree_waves, P));
+    const TriFactor &T = P.T;
+    *schedule = T.schedule;
+    for (int i = 0; i < 6; ++i) est[i] = T.est_us[i];
+    const int64_t v[8] = {T.levels, T.band.K, T.band.nblocks, T.band.ring_words, T.band.narrow ? 1 : 0,
+                          T.grid.K, T.grid.dict_n, T.lv.steps};
+    for (int i = 0; i < 8; ++i) info[i] = v[i];
     return PSK_OK;
 }
 

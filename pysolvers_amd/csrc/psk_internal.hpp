@@ -218,26 +218,27 @@ namespace psk {
 struct AmgHierarchy;
 
 // One sparse triangular factor on the device: off-diagonal entries in stored order (lower or
-// upper implied by the solve direction), diagonal (nullptr = unit), and two schedules built on
-// the host at creation (ilu.hip):
+// upper implied by the solve direction), diagonal (nullptr = unit), and the schedules the host planned
+// at creation (trisolve_plan.hip), each with a kernel file of its own (trisolve_<schedule>.hip):
 //  * sync-free: rows dealt to waves in dependency-level order (`order`, `levels` global levels);
-//  * band: solve order cut into `band_nblocks` contiguous blocks of `band_B` rows, one workgroup
+//  * band: solve order cut into `band.nblocks` contiguous blocks of `band.B` rows, one workgroup
 //    per block walking the block's LOCAL levels (dependencies inside the block) with a barrier
 //    between levels; dependencies on earlier blocks are waited on through the published values;
-//    an LDS ring of `ring_words` doubles (0 = none) serves the in-block dependencies.
+//    an LDS ring of `band.ring_words` doubles (0 = none) serves the in-block dependencies.
 //  * LDS: small factors (x fits LDS) solved by one workgroup, sync-free inside it with x in LDS.
-//  * grid: factors whose dependencies form a 2-D stencil in solve order (grid_w positions per line,
+//  * grid: factors whose dependencies form a 2-D stencil in solve order (grid.w positions per line,
 //    every dependency (lines back, positions back) within 63 lines and skewable):
 //    one wave per band of 64 lines, all 64 lines advancing together along the skewed coordinate
-//    u = x + g(y), g(y) = (grid_sigma * y + grid_phase) >> 1 (grid_sigma is TWICE the skew, so a
-//    half-integer skew is an odd grid_sigma), in-band dependencies through an LDS ring of the last
-//    grid_ring steps, only
-//    the band above through published values (sptrsv_grid_kernel).
+//    u = x + g(y), g(y) = (grid.sigma * y + grid.phase) >> 1 (grid.sigma is TWICE the skew, so a
+//    half-integer skew is an odd grid.sigma), in-band dependencies through an LDS ring of the last
+//    steps, only the band above through published values (sptrsv_grid_kernel).
 //  * part: rows cut into strips of their natural index, one workgroup per strip (per CU), the
 //    strip's own dependencies through an LDS cache, the others through published values
 //    (sptrsv_part_kernel).
-// `schedule` picks one (kSchedSyncFree / kSchedBand / kSchedLds / kSchedGrid / kSchedPart), chosen by host
-// cost models.
+//  * levels: few rows per dependency level: ONE workgroup, a level (or a piece of one) per step behind a
+//    barrier, every value in an LDS slot the host assigned (sptrsv_levels_kernel).
+// `schedule` picks one (kSchedSyncFree / kSchedBand / kSchedLds / kSchedGrid / kSchedPart / kSchedLevel), chosen
+// by host cost models (trisolve_plan.hip).
 enum TriSchedule : int { kSchedSyncFree = 0, kSchedBand = 1, kSchedLds = 2, kSchedGrid = 3, kSchedPart = 4,
                          kSchedLevel = 5 };
 constexpr int kGridMaxPE = 8;   // distinct dependency patterns reaching into the band above
@@ -245,63 +246,73 @@ struct GridExt {
     int32_t delta[kGridMaxPE];  // pattern code: ud * 64 + yd (steps back, lines back)
     int32_t yd[kGridMaxPE];     // lines back
 };
-// words of a factor's scheduling array (TriFactor::sched, ilu.hip): block tickets, publication counters, the
+// words of a factor's scheduling array (TriFactor::sched, trisolve.hpp): block tickets, publication counters, the
 // exit count and the workers the last sync-free launch enrolled, each on its own 256-B line
 constexpr int kSchedTicket = 0, kSchedPub = 64, kSchedExit = 128, kSchedLast = 192, kSchedWords = 256;
-// the grid of a sync-free triangular-solve launch (ilu.hip)
+// the grid of a sync-free triangular-solve launch (trisolve_syncfree.hip)
 int syncfree_grid(const Context *c);
+// One factor on the device: the common part, then one group per schedule whose layout was built (a group's
+// arrays are null and its scalars zero otherwise).
 struct TriFactor {
     bool present = false, upper = false;
     int64_t nnz = 0;
+    // the sync-free kernel's copy of the factor in solve order (position k = row order[k]); diag: nullptr = unit
     int32_t *rowptr = nullptr, *colidx = nullptr;
     double *vals = nullptr, *diag = nullptr;
     int32_t *order = nullptr;
     int64_t levels = 0;
     int schedule = kSchedSyncFree;
+    uint32_t *sched = nullptr;      // block tickets / worker enrolment of the spin-waiting schedules (trisolve.hpp)
+    double est_us[6] = {0.0, 0.0, -1.0, -1.0, -1.0, -1.0};   // the cost models' estimates by TriSchedule; -1: not eligible
     // band record stream (n records, block by block in local-level order; SoA, K entries each)
-    int32_t *rec_row = nullptr, *rec_end = nullptr, *rec_c = nullptr;
-    double *rec_v = nullptr, *rec_d = nullptr;
-    int band_K = 0;
-    int64_t band_B = 0, band_nblocks = 0, band_levels = 0;
-    int32_t ring_words = 0;
-    bool band_narrow = false;   // band run by sptrsv_band_narrow_kernel (local levels <= one wave wide)
-    // grid records in solve order q: K pattern codes (uint16, 0xFFFF = padding) and K values per row
-    // (row-major, stored entry order), diagonal (nullptr = unit)
-    uint16_t *gd_code = nullptr;
-    double *gd_coef = nullptr, *gd_diag = nullptr;
-    // record dictionary (grid_dict_n > 0): every lane-step's record is one of grid_dict_n distinct
-    // (codes, values, diagonal) records, gd_dict = [n][K] values, [n] diagonals, then [n][K/2] code
-    // words; gd_idx = the record index of each lane-step in the solver's access order
-    uint32_t *gd_idx = nullptr;
-    double *gd_dict = nullptr;
-    int grid_dict_n = 0;
-    int32_t *grid_flag = nullptr;   // dictionary kernel: a step's quotient needed the IEEE re-solve (zeroed after it)
-    uint32_t *sched = nullptr;      // block tickets / worker enrolment of the spin-waiting schedules (ilu.hip)
-    int grid_K = 0, grid_pe = 0, grid_maxyd = 0, grid_ring = 0;
-    int64_t grid_w = 0, grid_H = 0, grid_S = 0;   // grid_S: steps per band (slot stride)
-    int64_t grid_sigma = 0, grid_phase = 0;      // g(y) = (grid_sigma * y + grid_phase) >> 1 (twice the skew)
-    int64_t grid_off = 0;   // empty grid positions before the first row (a partial first line)
-    GridExt grid_ext{};
-    // part layout: position k = part_seg[w] + q (workgroup w's q-th row); rows, entries (codes) in it
-    int64_t *part_seg = nullptr;
-    int32_t *part_rp = nullptr, *part_code = nullptr, *part_row = nullptr;
-    double *part_va = nullptr;
-    int part_P = 0;
-    // levels layout (round 5, sptrsv_levels_kernel): ONE workgroup of lv_W lanes, a dependency level (or a
-    // lv_W-row piece of one) per step behind a barrier, x in lv_R LDS slots the host assigns (a value's slot
-    // is free again after the step of its last reader; slot lv_R holds 0.0, slot lv_R + 1 takes the values
-    // nobody reads). Per step s and lane t (field-major, coalesced): lv_rc = row | (write slot << 40)
-    // (row 0xFFFFFFFF: idle lane), lv_sl = slots of the entries, four uint16 per word (padding: slot lv_R),
-    // lv_cf = coefficients in stored order (padding -0.0), two per 16 bytes, lv_dg = diagonal (1.0 for a
-    // unit factor), lv_b = the right-hand side gathered into step order before each solve
-    uint64_t *lv_rc = nullptr;
-    uint64_t *lv_sl = nullptr;
-    double *lv_cf = nullptr, *lv_dg = nullptr, *lv_b = nullptr;
-    int64_t lv_steps = 0;
-    int lv_W = 0, lv_R = 0, lv_KM = 0;
-    double est_syncfree_us = 0.0, est_band_us = 0.0, est_lds_us = -1.0, est_grid_us = -1.0, est_part_us = -1.0;
-    double est_level_us = -1.0;
-    // 5-point grid signature of an upper factor (make_factor; amg.hip's paired Gauss-Seidel sweeps): n = fd5_m * H,
+    struct Band {
+        int32_t *rec_row = nullptr, *rec_end = nullptr, *rec_c = nullptr;
+        double *rec_v = nullptr, *rec_d = nullptr;
+        int K = 0;
+        int64_t B = 0, nblocks = 0;
+        int32_t ring_words = 0;
+        bool narrow = false;   // run by sptrsv_band_narrow_kernel (local levels <= one wave wide)
+        void release();
+    } band;
+    // grid records, one GridStep block per (band, step) in the solver's access order (coef), or the record
+    // dictionary (dict_n > 0): every lane-step's record is one of dict_n distinct (codes, values, diagonal)
+    // records, dict = [n][K] values, [n] diagonals, then [n][K/2] code words; idx = the record index of each
+    // lane-step in the solver's access order
+    struct Grid {
+        double *coef = nullptr, *dict = nullptr;
+        uint32_t *idx = nullptr;
+        int dict_n = 0;
+        int32_t *flag = nullptr;   // dictionary kernel: a step's quotient needed the IEEE re-solve (zeroed after it)
+        int K = 0, pe = 0, maxyd = 0;
+        int64_t w = 0, H = 0, S = 0;   // S: steps per band (slot stride)
+        int64_t sigma = 0, phase = 0;  // g(y) = (sigma * y + phase) >> 1 (twice the skew)
+        int64_t off = 0;   // empty grid positions before the first row (a partial first line)
+        GridExt ext{};
+        void release();
+    } grid;
+    // part layout: position k = seg[w] + q (workgroup w's q-th row); rows, entries (codes) in it
+    struct Part {
+        int64_t *seg = nullptr;
+        int32_t *rp = nullptr, *code = nullptr, *row = nullptr;
+        double *va = nullptr;
+        int P = 0;
+        void release();
+    } part;
+    // levels layout (sptrsv_levels_kernel): ONE workgroup of W lanes, a dependency level (or a W-row piece of
+    // one) per step behind a barrier, x in R LDS slots the host assigns (a value's slot is free again after the
+    // step of its last reader; slot R holds 0.0, slot R + 1 takes the values nobody reads). Per step s and lane t
+    // (field-major, coalesced): rc = row | (write slot << 40) (row 0xFFFFFFFF: idle lane), sl = slots of the
+    // entries, four uint16 per word (padding: slot R), cf = coefficients in stored order (padding -0.0), two per
+    // 16 bytes, dg = diagonal (1.0 for a unit factor), b = the right-hand side gathered into step order before
+    // each solve
+    struct Levels {
+        uint64_t *rc = nullptr, *sl = nullptr;
+        double *cf = nullptr, *dg = nullptr, *b = nullptr;
+        int64_t steps = 0;
+        int W = 0, R = 0, KM = 0;
+        void release();
+    } lv;
+    // 5-point grid signature of an upper factor (detect_fd5; amg.hip's paired Gauss-Seidel sweeps): n = fd5_m * H,
     // row i's off-diagonal entries exactly columns i + 1 (i % m < m - 1) and i + m (i + m < n), values fd5_a1 / fd5_am,
     // every diagonal fd5_d, fd5_mfirst = the +m entry stored before the +1 entry. fd5_m = 0: no such signature.
     int64_t fd5_m = 0;

@@ -479,7 +479,7 @@ def test_amg_dense_vs_lu_coarse(psk):
 
 
 # ---------------------------------------------------------------------------------------------
-# levels schedule (round 5, ilu.hip sptrsv_levels_kernel): one workgroup, a dependency level per step
+# levels schedule (round 5, trisolve_levels.hip sptrsv_levels_kernel): one workgroup, a dependency level per step
 # behind a barrier, x in an LDS ring. Bars: bit-identical to the band and grid schedules (the same per-row
 # arithmetic: fma over the stored entries in stored order from 0.0, then (b - acc) / d), 1e-12 against
 # scipy on random chains with permutations, and the SA level-1 Gauss-Seidel factor it is planned for.

@@ -107,18 +107,22 @@ def test_gs_pair_not_eligible_keeps_serialized(psk, lab, how):
 
 
 @pytest.mark.parametrize("m", [32, 96, 200])
-@pytest.mark.parametrize("sched", ["syncfree", "lds", "band", "grid"])
-def test_gs_pair_follows_the_schedule_arithmetic(psk, lab, m, sched):
+@pytest.mark.parametrize("sched", ["syncfree", "lds", "band", "grid", "part", "levels"])
+def test_gs_pair_follows_the_schedule_arithmetic(psk, lab, m, sched, monkeypatch):
     """-FD m^2 (FDBratu2D.py:15; values 4/h^2, -1/h^2: rounded products) with the fine smoother's schedule
-    forced: pairing on == off bitwise under each."""
+    forced: pairing on == off bitwise under each. The partitioned and levels layouts exist only when built
+    at creation, so those two cases ask for them in the environment before form()."""
     from oracle import fdlap
+    if sched in ("part", "levels"):
+        monkeypatch.setenv({"part": "PSK_TRISOLVE_PART", "levels": "PSK_TRISOLVE_LEVELS"}[sched], "1")
     A = -fdlap.fd_laplacian_2d(-1.0, 1.0, m)
     v = np.random.default_rng(m).standard_normal(A.shape[0])
     M = psk.AMG(numIters=2, numLevels=2).form(A)
     S = M._S[-1].operator
     try:
         S.schedule("U", set=sched)
-    except Exception as e:   # grid: small factors have no grid plan; lds: too large for one workgroup
+    except Exception as e:   # grid: small factors have no grid plan; lds: too large for one workgroup;
+        # part: factors that fit one workgroup's LDS schedule get no partitioned layout
         pytest.skip("schedule %s not available: %s" % (sched, e))
     assert S.schedule("U")["schedule"] == sched
     on, el = pair(lab, M, 1)

@@ -1,4 +1,4 @@
-"""The partitioned triangular-solve schedule (sptrsv_part_kernel, ilu.hip): strips of the natural
+"""The partitioned triangular-solve schedule (sptrsv_part_kernel, trisolve_part.hip): strips of the natural
 index per workgroup, in-strip dependencies through an LDS cache. It runs the sync-free kernel's
 per-row arithmetic, so every test checks it bit for bit against the sync-free schedule on the same
 factor, and against the host reference solve (SuperLU ILU.solve / spsolve_triangular) to 1e-12.

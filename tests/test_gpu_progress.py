@@ -9,7 +9,7 @@ no expired wait and without the occupiers reaching their time limit.
 
 Before round 5 the sync-free schedule dealt row k to wave k mod W of a grid sized to the device and the
 band schedule block b to workgroup b mod g: with part of that grid unable to start, the resident waves
-spun on rows nobody would ever solve (ilu.hip "forward progress without co-residency").
+spun on rows nobody would ever solve (trisolve.hpp "forward progress without co-residency").
 Bar: bit-exact against the same factor's solve on an idle device (same schedule, same per-row arithmetic).
 """
 import ctypes

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Host model of the strip triangular-solve schedule (lab tool; restates ilu.hip plan_strip):
+"""Host model of the strip triangular-solve schedule (lab tool; restates trisolve_plan.hip plan_part):
 strips of the natural index, rows in ASAP order packed greedily into steps of <= 64 independent
 rows, then an event simulation of the solve (a step starts when its strip's previous step ended
 and every external dependency was published + the cross-CU hand-off). Checks that every local
