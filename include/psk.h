@@ -83,6 +83,8 @@ extern "C" {
 #define PSK_PREC_AMG      3      /* smoothed-aggregation V-cycles  AMGPreconditioner.py:46-51 */
 #define PSK_PREC_DENSE    4      /* x = A^-1 f by a dense inverse: the AMG coarse solve spsolve(A_c, f),
                                     VCycleManager.py:34-37 (psk_prec_create_dense_inverse) */
+#define PSK_PREC_CHEBYSHEV 5     /* Chebyshev polynomial in D^-1 A (psk_prec_create_chebyshev); no reference
+                                    counterpart (the reference's smoothers are Jacobi and Gauss-Seidel) */
 
 typedef struct psk_csr  psk_csr;    /* device CSR (int32 rowptr/colidx, f64 vals), library-owned */
 typedef struct psk_prec psk_prec;   /* formed preconditioner, library-owned */
@@ -243,12 +245,29 @@ int psk_prec_create_trisolve(int64_t n, const int32_t *l_rowptr, const int32_t *
  * PSK_ERR_UNSUPPORTED when n > 32768 (8.6 GB) or rocSOLVER cannot be loaded, PSK_ERR_ARG when A is
  * singular. The input vector of an apply must be 16-byte aligned. */
 int psk_prec_create_dense_inverse(const psk_csr *A, int32_t refine, psk_prec **out);
+/* Chebyshev polynomial preconditioner / smoother of `degree` >= 1 in D^-1 A, D = diag(A) (the Jacobi DInv),
+ * for the eigenvalues of D^-1 A in [lmax/ratio, lmax]; f64, every operation rounded as written:
+ *   lmin = lmax/ratio, theta = (lmax+lmin)/2, delta = (lmax-lmin)/2, sigma = theta/delta, rho_0 = 1/sigma,
+ *   c0 = 1/theta; for k = 1..degree-1: rho_k = 1/(2 sigma - rho_{k-1}), alpha_k = rho_k rho_{k-1},
+ *   beta_k = 2 rho_k/delta (host doubles);
+ *   apply z = M^-1 v: d = c0 (DInv v), z = d; then for k = 1..degree-1, ONE launch each:
+ *   d = alpha_k d + beta_k (DInv (v - A z)), z = z + d, the row sums of A z as psk_spmv forms them.
+ * degree 1 is Jacobi scaled by c0. lmax <= 0 selects the Gershgorin bound max_i (sum_j |a_ij|) |DInv_i| (row sums
+ * in stored order), a true upper bound, so the operator is definite for a definite A; ratio > 1 (30 is customary
+ * for a smoother). Symmetric for symmetric A: usable by PCG, by GMRES and as an AMG smoother
+ * (psk_prec_create_amg). Each step streams A once (CSR arrays), has no dependency chain and no grid sum.
+ * A is BORROWED. PSK_ERR_ARG: degree < 1, ratio <= 1, A not square or empty, a diagonal entry that is zero,
+ * missing or not finite; PSK_ERR_UNSUPPORTED: a sharded A. Replaces nothing in the reference. */
+int psk_prec_create_chebyshev(const psk_csr *A, int32_t degree, double lmax, double ratio, psk_prec **out);
+/* The formed polynomial: coeffs (nullable) receives 2*degree-1 doubles, c0 then the (alpha_k, beta_k) pairs of
+ * k = 1..degree-1. Any out pointer may be NULL. PSK_ERR_ARG when M is not a PSK_PREC_CHEBYSHEV. */
+int psk_prec_chebyshev_info(const psk_prec *M, int32_t *degree, double *lmax, double *lmin, double *coeffs);
 /* Smoothed-aggregation AMG preconditioner over a host-built hierarchy (levels 0 = coarsest ..
  * num_levels-1 = finest, MLHierarchy.py:250-258). Arrays of num_levels handles, all BORROWED
  * (they must outlive the preconditioner): A[k] level matrices (A[num_levels-1] = the fine A),
  * P[k] (n_{k+1} x n_k) and R[k] (n_k x n_{k+1}) for k < num_levels-1, smoother[k] for k >= 1
  * (any preconditioner S: one sweep is x <- x + S^-1 (f - A x): PSK_PREC_ILU upper solve with
- * triu(A_k) = Gauss-Seidel, PSK_PREC_JACOBI = Jacobi; ClassicSmoothers.py:5-36), coarse = the
+ * triu(A_k) = Gauss-Seidel, PSK_PREC_JACOBI = Jacobi; ClassicSmoothers.py:5-36; PSK_PREC_CHEBYSHEV), coarse = the
  * level-0 direct solve. apply(v): x = v; num_iters V-cycles, stopping after the first cycle whose
  * ||v - A x|| < tau ||v|| (VCycleSolver.py:119-146). */
 int psk_prec_create_amg(int32_t num_levels, psk_csr *const *A, psk_csr *const *P, psk_csr *const *R,

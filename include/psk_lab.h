@@ -52,6 +52,11 @@ int psk_lab_spmv_rotate(const psk_csr *A, const double *const *xs, double *const
  * p the next SpMV gathers), 2 = it writes `scratch` (another buffer of n doubles). reps <= 256. */
 int psk_lab_spmv_after_write(const psk_csr *A, double *x, double *y, const double *src, double *scratch,
                              int32_t target, int32_t reps, int32_t dot, double *avg_ms);
+/* Lab (tools/cheby_ab.py): one Chebyshev step (PSK_PREC_CHEBYSHEV handle of degree >= 3, device vector v) timed two
+ * ways between HIP events on the library stream, reps launches back to back after one untimed step: the fused
+ * launch (cheby_step_kernel), and the same update composed of the residual SpMV in A's current layout, the DInv
+ * scale, the d update and the z update (four launches). Milliseconds per step. */
+int psk_lab_cheby_ab(const psk_prec *M, const double *v, int32_t reps, double *fused_ms, double *pieces_ms);
 #ifdef __cplusplus
 }
 #endif

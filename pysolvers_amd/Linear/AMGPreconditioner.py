@@ -7,8 +7,8 @@ failOnMaxiter=False) (VCycleSolver.py:52-95) runs entirely on the device (psk_pr
 pysolvers_amd/csrc/amg.hip): numIters V-cycles from x0 = v, early exit on ||v - A x|| < 1e-8 ||v||.
 
 Level operators: SpMV (bit-identical stored-order sums) for A_k, R_k, P_k; smoothing sweeps
-x <- x + S^-1 (f - A x) with S^-1 = DInv* (Jacobi) or triu(A_k)^-1 (Gauss-Seidel, sync-free
-triangular solve); the coarsest level is spsolve(A_0, f) (VCycleManager.py:34-37; the reference
+x <- x + S^-1 (f - A x) with S^-1 = DInv* (Jacobi), triu(A_k)^-1 (Gauss-Seidel, sync-free
+triangular solve) or a Chebyshev polynomial in DInv A_k (ChebyshevSmoother; not in the reference); the coarsest level is spsolve(A_0, f) (VCycleManager.py:34-37; the reference
 refactors A_0 on every call, same factors each time). Since round 5 that solve is a streamed GEMV over
 A_0^-1, formed once on the device (coarse="dense", pysolvers_amd/csrc/dense.hip): one HBM-bound pass
 instead of a sparse triangular-solve chain thousands of dependency levels deep (4.84 -> ~0.4 ms at
@@ -24,7 +24,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from .. import _native as N
-from .ClassicSmoothers import GaussSeidelSmoother, JacobiSmoother
+from .ClassicSmoothers import GaussSeidelSmoother, _Smoother
 from .DeviceMatrix import DeviceCSR
 from .Preconditioner import DeviceOperator, GenericPreconditioner
 from .PreconditionerType import PreconditionerType
@@ -93,8 +93,9 @@ class AMGPreconditioner(DeviceOperator, GenericPreconditioner):
 
     def __init__(self, A, numIters=5, numLevels=2, nuPre=2, nuPost=2, smoother=GaussSeidelSmoother, tau=1.0e-8,
                  coarse="auto", coarse_refine=None):
-        if smoother not in (GaussSeidelSmoother, JacobiSmoother):
-            raise TypeError("AMG smoother must be GaussSeidelSmoother or JacobiSmoother")
+        if not (isinstance(smoother, type) and issubclass(smoother, _Smoother) and smoother is not _Smoother):
+            raise TypeError("AMG smoother must be a smoother class with a device operator: GaussSeidelSmoother, "
+                            "JacobiSmoother, ChebyshevSmoother or ChebyshevSmoother.of(...)")
         if coarse not in ("auto", "dense", "lu"):
             raise ValueError("AMG coarse must be 'auto', 'dense' or 'lu'")
         dA = A if isinstance(A, DeviceCSR) else DeviceCSR.from_scipy(A)
@@ -108,6 +109,8 @@ class AMGPreconditioner(DeviceOperator, GenericPreconditioner):
         self._P = [DeviceCSR.from_scipy(self.mlh.update(k), rectangular=True) for k in range(L - 1)]
         self._R = [DeviceCSR.from_scipy(self.mlh.downdate(k), rectangular=True) for k in range(L - 1)]
         self._S = [None] + [smoother(self.mlh.matrix(k), device_A=self._A[k]) for k in range(1, L)]
+        if any(getattr(getattr(s, "operator", None), "device_handle", None) is None for s in self._S[1:]):
+            raise TypeError("AMG smoother %s provides no device operator" % smoother.__name__)
         self._coarse, self._lu, self.coarse_kind = None, None, "lu"
         # auto: the dense inverse with one refinement step x += A_0^-1 (f - A_0 x) (the inverse's forward
         # error grows with cond(A_0) where spsolve's LU is backward stable; one step brings it back to the LU's

@@ -3,6 +3,7 @@
 Both of the reference's smoothers are a sweep x <- x + S^-1 (f - A x):
 * JacobiSmoother      S^-1 r = DInv * r, DInv = reciprocal(diag A)      (:5-14)
 * GaussSeidelSmoother S^-1 r = spsolve(triu(A), r)                      (:28-36)
+* ChebyshevSmoother   S^-1 r = p(D^-1 A) D^-1 r, p the Chebyshev polynomial of a degree (no reference counterpart)
 Each class builds that S^-1 as a device operator (``.operator``); the V-cycle itself runs inside
 libpsk (psk_prec_create_amg). ``apply(f, x, nu)`` keeps the reference's host-callable contract.
 """
@@ -10,7 +11,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from .DeviceMatrix import DeviceCSR, spmv
-from .Preconditioner import JacobiPreconditioner
+from .Preconditioner import ChebyshevPreconditioner, JacobiPreconditioner
 from .TriangularSolve import TriangularSolveChain
 
 
@@ -43,3 +44,23 @@ class GaussSeidelSmoother(_Smoother):
         super().__init__(A, device_A)
         self.U = sp.triu(_host(A)).tocsr()              # :33
         self.operator = TriangularSolveChain(self.U.shape[0], U=self.U, u_unit=False)
+
+
+class ChebyshevSmoother(_Smoother):
+    """S^-1 r = the Chebyshev polynomial of ``degree`` in D^-1 A applied to D^-1 r (ChebyshevPreconditioner on the
+    level's device matrix). No reference counterpart: a smoother without a triangular solve. The class itself
+    means degree 2, ratio 30 and the Gershgorin bound; ``ChebyshevSmoother.of(...)`` gives a configured subclass
+    (``smoother=`` takes a class)."""
+
+    degree, ratio, lmax = 2, 30.0, None
+
+    def __init__(self, A, device_A=None):
+        super().__init__(A, device_A)
+        self.operator = ChebyshevPreconditioner(self._dA, degree=self.degree, lmax=self.lmax, ratio=self.ratio)
+
+    @classmethod
+    def of(cls, degree=2, ratio=30.0, lmax=None):
+        """A subclass with these settings. One lmax serves every level: leave it None (each level's own
+        Gershgorin bound) unless the levels share a bound."""
+        name = "ChebyshevSmoother_d%d" % int(degree)
+        return type(name, (cls,), dict(degree=int(degree), ratio=float(ratio), lmax=lmax))

@@ -131,3 +131,56 @@ class JacobiPreconditioner(DeviceOperator, GenericPreconditioner):
 
     def apply(self, vec):
         return self._device_apply(vec)
+
+
+class ChebyshevPreconditioner(DeviceOperator, GenericPreconditioner):
+    """M^-1 v = the degree-``degree`` Chebyshev polynomial in D^-1 A applied to D^-1 v, D = diag(A), for the
+    eigenvalues of D^-1 A in [lmax/ratio, lmax] (psk_prec_create_chebyshev, pysolvers_amd/csrc/cheby.hip).
+
+    No reference counterpart (the reference's smoothers are Jacobi and Gauss-Seidel, ClassicSmoothers.py:5-36):
+    the strong smoother without a triangular solve. One pass over A per degree beyond the first, no dependency
+    chain; symmetric for symmetric A, so PCG may use it on its own or inside the AMG V-cycle. ``lmax=None`` takes
+    the Gershgorin bound of D^-1 A (a true upper bound, loose on badly scaled matrices: pass an estimate of
+    the largest eigenvalue then). ``degree=1`` is Jacobi scaled by 1/theta.
+    """
+
+    device_kind = N.PSK_PREC_CHEBYSHEV
+
+    def __init__(self, A, degree=3, lmax=None, ratio=30.0):
+        self._A = as_device_matrix(A)        # borrowed by the handle: keep it alive
+        h = ctypes.c_void_p()
+        N.check(N.lib.psk_prec_create_chebyshev(self._A.handle, int(degree), 0.0 if lmax is None else float(lmax),
+                                                float(ratio), ctypes.byref(h)), "psk_prec_create_chebyshev")
+        self._h = h
+        self.n = self._A.n
+        self.ratio = float(ratio)
+
+    def _info(self):
+        k, hi, lo = N.I32(), N.F64(), N.F64()
+        N.check(N.lib.psk_prec_chebyshev_info(self._h, ctypes.byref(k), ctypes.byref(hi), ctypes.byref(lo), None),
+                "psk_prec_chebyshev_info")
+        return k.value, hi.value, lo.value
+
+    @property
+    def degree(self):
+        return self._info()[0]
+
+    @property
+    def lmax(self):
+        """Upper end of the interval: the caller's, or the Gershgorin bound of D^-1 A."""
+        return self._info()[1]
+
+    @property
+    def lmin(self):
+        """lmax / ratio."""
+        return self._info()[2]
+
+    @property
+    def coefficients(self):
+        """c0, then (alpha_k, beta_k) for k = 1..degree-1: 2*degree - 1 doubles (include/psk.h)."""
+        c = np.empty(2 * self.degree - 1, dtype=np.float64)
+        N.check(N.lib.psk_prec_chebyshev_info(self._h, None, None, None, N.ptr(c)), "psk_prec_chebyshev_info")
+        return c
+
+    def apply(self, vec):
+        return self._device_apply(vec)

@@ -1,7 +1,7 @@
 """Preconditioner factories (PreconditionerType.py:4-19): ``form(A)`` builds the operator."""
 from abc import ABC, abstractmethod
 
-from .Preconditioner import IdentityPreconditioner, JacobiPreconditioner
+from .Preconditioner import ChebyshevPreconditioner, IdentityPreconditioner, JacobiPreconditioner
 
 
 class PreconditionerType(ABC):
@@ -26,3 +26,19 @@ class JacobiPreconditionerType(PreconditionerType):
 
 # short factory name in the style of RightILUT()/RightIC()/AMG()
 Jacobi = JacobiPreconditionerType
+
+
+class ChebyshevPreconditionerType(PreconditionerType):
+    """Chebyshev polynomial preconditioner of ``degree`` in D^-1 A (ChebyshevPreconditioner); ``lmax=None``:
+    the Gershgorin bound."""
+
+    def __init__(self, degree=3, lmax=None, ratio=30.0):
+        self.degree = degree
+        self.lmax = lmax
+        self.ratio = ratio
+
+    def form(self, A):
+        return ChebyshevPreconditioner(A, degree=self.degree, lmax=self.lmax, ratio=self.ratio)
+
+
+Chebyshev = ChebyshevPreconditionerType

@@ -1,6 +1,6 @@
 """Drop-in for PySolvers.Linear's PCG/GMRES path (Linear/__init__.py:1-12 names)."""
 from .AMGPreconditioner import AMG, AMGPreconditioner
-from .ClassicSmoothers import GaussSeidelSmoother, JacobiSmoother
+from .ClassicSmoothers import ChebyshevSmoother, GaussSeidelSmoother, JacobiSmoother
 from .DeviceMatrix import DeviceCSR, DeviceVector, spmv
 from .DirectSolver import DefaultDirect, DefaultDirectSolver
 from .Distributed import Communicator, fd_laplacian_2d_sharded, halo_cols, shard_csr
@@ -12,10 +12,10 @@ from .IterativeLinearSolver import IterativeLinearSolver, IterativeLinearSolverT
 from .LinearSolver import LinearSolver, LinearSolverType
 from .PCGSolver import PCG, PCGSolver
 from .MLHierarchy import MLHierarchy, makeRestrictionOp
-from .Preconditioner import (DeviceOperator, GenericPreconditioner, IdentityPreconditioner, JacobiPreconditioner,
-                             LeftPreconditioner, Preconditioner, RightPreconditioner)
-from .PreconditionerType import (IdentityPreconditionerType, Jacobi, JacobiPreconditionerType,
-                                 PreconditionerType)
+from .Preconditioner import (ChebyshevPreconditioner, DeviceOperator, GenericPreconditioner, IdentityPreconditioner,
+                             JacobiPreconditioner, LeftPreconditioner, Preconditioner, RightPreconditioner)
+from .PreconditionerType import (Chebyshev, ChebyshevPreconditionerType, IdentityPreconditionerType, Jacobi,
+                                 JacobiPreconditionerType, PreconditionerType)
 from .SmoothedAggregation import SA_coarsen, SmoothedAggregationMLHierarchy
 from .TriangularSolve import TriangularSolveChain
 from .VCycleSolver import AMGVCycle, AMGVCycleSolver

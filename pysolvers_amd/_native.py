@@ -20,7 +20,7 @@ PSK_CONVERGED, PSK_MAXITER, PSK_BREAKDOWN, PSK_TRUE_RESID_FAIL = 0, 1, 2, 3
 PSK_EXIT_NONE, PSK_EXIT_TOLERANCE, PSK_EXIT_ARNOLDI_BREAKDOWN, PSK_EXIT_MAXITER, PSK_EXIT_DOT_BREAKDOWN = 0, 1, 2, 3, 4
 PSK_HOST, PSK_DEVICE = 0, 1
 PSK_VCYCLE_X0_GIVEN = 1   # psk_vcycle flags: x holds the starting iterate
-PSK_PREC_IDENTITY, PSK_PREC_JACOBI, PSK_PREC_ILU, PSK_PREC_AMG, PSK_PREC_DENSE = 0, 1, 2, 3, 4
+PSK_PREC_IDENTITY, PSK_PREC_JACOBI, PSK_PREC_ILU, PSK_PREC_AMG, PSK_PREC_DENSE, PSK_PREC_CHEBYSHEV = 0, 1, 2, 3, 4, 5
 PSK_LAYOUT_CSR, PSK_LAYOUT_SLICED, PSK_LAYOUT_SLICED_WIDE, PSK_LAYOUT_SLICED_DICT, PSK_LAYOUT_DIAG = 0, 1, 2, 3, 4
 PSK_UNIQUE_ID_BYTES = 128
 
@@ -80,6 +80,8 @@ SIGNATURES = {
     "psk_prec_create_trisolve": (ctypes.c_int, [I64, P, P, P, I32, P, P, P, I32, P, P, PP]),
     "psk_prec_create_amg": (ctypes.c_int, [I32, PP, PP, PP, PP, P, I32, I32, I32, F64, PP]),
     "psk_prec_create_dense_inverse": (ctypes.c_int, [P, I32, PP]),
+    "psk_prec_create_chebyshev": (ctypes.c_int, [P, I32, F64, F64, PP]),
+    "psk_prec_chebyshev_info": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(F64), ctypes.POINTER(F64), P]),
     "psk_prec_trisolve_schedule": (ctypes.c_int, [P, I32, I32, ctypes.POINTER(I32), ctypes.POINTER(I64),
                                                    ctypes.POINTER(I32), ctypes.POINTER(F64), ctypes.POINTER(F64)]),
     "psk_prec_trisolve_grid_info": (ctypes.c_int, [P, I32, ctypes.POINTER(I64)]),
@@ -121,6 +123,7 @@ LAB_SIGNATURES = {
                                              ctypes.POINTER(F64), ctypes.POINTER(I64)]),
     "psk_lab_amg_gs_pair": (ctypes.c_int, [P, I32, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
     "psk_lab_spmv_rotate": (ctypes.c_int, [P, ctypes.POINTER(P), ctypes.POINTER(P), I32, I32, I32, ctypes.POINTER(F64)]),
+    "psk_lab_cheby_ab": (ctypes.c_int, [P, P, I32, ctypes.POINTER(F64), ctypes.POINTER(F64)]),
     "psk_lab_spmv_after_write": (ctypes.c_int, [P, P, P, P, P, I32, I32, I32, ctypes.POINTER(F64)]),
 }
 _lab = None

@@ -177,6 +177,10 @@ extern "C" int psk_lab_trisolve_plan(int64_t n, const int32_t *rowptr, const int
     return PSK_OK;
 }
 
+extern "C" int psk_lab_cheby_ab(const psk_prec *M, const double *v, int32_t reps, double *fused_ms, double *pieces_ms) {
+    return psk::cheby_ab(M, v, reps, fused_ms, pieces_ms);
+}
+
 extern "C" int psk_lab_amg_gs_pair(psk_prec *M, int32_t set, int32_t *levels_on, int32_t *levels_eligible) {
     using namespace psk;
     if (set < -1 || set > 1) return fail(PSK_ERR_ARG, "psk_lab_amg_gs_pair: set must be -1, 0 or 1");

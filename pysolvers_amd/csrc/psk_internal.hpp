@@ -122,6 +122,7 @@ struct HaloPeer {
 
 struct ShmComm;
 struct DenseInverse;
+struct Chebyshev;
 // largest dense coarse inverse (psk_prec_create_dense_inverse): 32768^2 doubles = 8.6 GB
 constexpr int64_t kDenseMaxN = 32768;
 
@@ -335,6 +336,7 @@ struct psk_prec {
     int32_t *err = nullptr;
     psk::AmgHierarchy *amg = nullptr;   // PSK_PREC_AMG
     psk::DenseInverse *dense = nullptr; // PSK_PREC_DENSE (dense.hip)
+    psk::Chebyshev *cheb = nullptr;     // PSK_PREC_CHEBYSHEV (cheby.hip)
 };
 
 namespace psk {
@@ -970,10 +972,15 @@ int amg_residual(const psk_prec *M, const double *v, hipStream_t s);            
 int dense_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);
 int dense_check_error(const psk_prec *M, hipStream_t s);
 void dense_free(DenseInverse *d);
-// preconditioners whose apply is not a single elementwise op (triangular solves, AMG): the
+int cheby_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);   // cheby.hip; out must not alias v
+void cheby_free(Chebyshev *ch);
+// measurement: ms per step of `reps` back-to-back fused steps, and of the same step as four launches (cheby.hip)
+int cheby_ab(const psk_prec *M, const double *v, int reps, double *fused_ms, double *pieces_ms);
+// preconditioners whose apply is not a single elementwise op (triangular solves, AMG, polynomials): the
 // Krylov drivers take their general path for these
 inline bool prec_is_general(const psk_prec *M) {
-    return M && (M->kind == PSK_PREC_ILU || M->kind == PSK_PREC_AMG || M->kind == PSK_PREC_DENSE);
+    return M && (M->kind == PSK_PREC_ILU || M->kind == PSK_PREC_AMG || M->kind == PSK_PREC_DENSE ||
+                 M->kind == PSK_PREC_CHEBYSHEV);
 }
 // reports a bounded-spin timeout of any triangular solve inside M (syncs the stream)
 int prec_check_error(const psk_prec *M, hipStream_t s);

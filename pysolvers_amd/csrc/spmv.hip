@@ -2076,6 +2076,7 @@ int prec_apply_dev(const psk_prec *M, int64_t n, const double *v, double *out, h
     if (M->kind == PSK_PREC_ILU) return ilu_apply(M, v, out, s);
     if (M->kind == PSK_PREC_AMG) return amg_apply(M, v, out, s);
     if (M->kind == PSK_PREC_DENSE) return dense_apply(M, v, out, s);
+    if (M->kind == PSK_PREC_CHEBYSHEV) return cheby_apply(M, v, out, s);
     return fail(PSK_ERR_UNSUPPORTED, "unknown preconditioner kind");
 }
 
@@ -2489,6 +2490,7 @@ int psk_prec_destroy(psk_prec *M) {
     M->up.release();
     if (M->amg) amg_free(M->amg);
     if (M->dense) dense_free(M->dense);
+    if (M->cheb) cheby_free(M->cheb);
     delete M;
     return PSK_OK;
 }
