@@ -57,6 +57,23 @@ int psk_lab_spmv_after_write(const psk_csr *A, double *x, double *y, const doubl
  * launch (cheby_step_kernel), and the same update composed of the residual SpMV in A's current layout, the DInv
  * scale, the d update and the z update (four launches). Milliseconds per step. */
 int psk_lab_cheby_ab(const psk_prec *M, const double *v, int32_t reps, double *fused_ms, double *pieces_ms);
+/* Lab / tests of the PCG loop's staggered x flush (pcg_state.hpp); the first two touch no GPU.
+ * psk_lab_pcg_stagger: *blocks = S, the row blocks the build flushes in turn (0: built with the uniform flush only),
+ * *ring = the depth of the ring of p buffers. psk_lab_pcg_flush_schedule: the one schedule function the SpMV's flush
+ * role, K3, pcg_flush_kernel and the host call, for any S >= 1: *blk = the block of K3 tile `tile` of nv, and
+ * first_last[2] = the first and last iteration whose x update is pending for that block when the flush role of SpMV
+ * launch k runs (in_spmv = 1; the launch serves block k mod S) or when K3 / pcg_flush_kernel of iteration k runs
+ * (in_spmv = 0); first > last: none; first == 0: the block was never stored (x is the implicit 0).
+ * psk_lab_pcg_flush: pcg_flush_kernel as after a breakdown at iteration k >= 1 on host vectors: x[n] (in and out),
+ * ring[ring depth][n] (row j = the buffer of p_i, i mod depth == j), alphas[k]; stag = 1 per-block ranges, 0 the
+ * uniform rule. */
+int psk_lab_pcg_stagger(int32_t *blocks, int32_t *ring);
+/* *on = 1 when psk_pcg of matrix A in its current SpMV layout with preconditioner M (NULL: none) takes the staggered
+ * flush, 0 when it keeps the uniform flush in K3. */
+int psk_lab_pcg_staggers(const psk_csr *A, const psk_prec *M, int32_t *on);
+int psk_lab_pcg_flush_schedule(int32_t S, int64_t nv, int64_t tile, int64_t k, int32_t in_spmv, int32_t *blk,
+                               int64_t *first_last);
+int psk_lab_pcg_flush(int64_t n, int64_t k, int32_t stag, double *x, const double *ring, const double *alphas);
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,10 @@ LAB_SIGNATURES = {
     "psk_lab_spmv_rotate": (ctypes.c_int, [P, ctypes.POINTER(P), ctypes.POINTER(P), I32, I32, I32, ctypes.POINTER(F64)]),
     "psk_lab_cheby_ab": (ctypes.c_int, [P, P, I32, ctypes.POINTER(F64), ctypes.POINTER(F64)]),
     "psk_lab_spmv_after_write": (ctypes.c_int, [P, P, P, P, P, I32, I32, I32, ctypes.POINTER(F64)]),
+    "psk_lab_pcg_stagger": (ctypes.c_int, [ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+    "psk_lab_pcg_staggers": (ctypes.c_int, [P, P, ctypes.POINTER(I32)]),
+    "psk_lab_pcg_flush_schedule": (ctypes.c_int, [I32, I64, I64, I64, I32, ctypes.POINTER(I32), ctypes.POINTER(I64)]),
+    "psk_lab_pcg_flush": (ctypes.c_int, [I64, I64, I32, P, P, P]),
 }
 _lab = None
 

@@ -4,6 +4,7 @@
 // enrolment count of the last sync-free triangular-solve launch. Declared in include/psk_lab.h; nothing in the
 // product path calls them.
 #include "trisolve.hpp"
+#include "pcg_state.hpp"
 #include "../../include/psk_lab.h"
 
 #include <chrono>
@@ -281,5 +282,60 @@ extern "C" int psk_lab_spmv_after_write(const psk_csr *A, double *x, double *y, 
     }
     part.release();
     if (rc == PSK_OK) *avg_ms = tot / reps;
+    return rc;
+}
+
+// ---- the PCG loop's staggered x flush (pcg_state.hpp): its schedule as the kernels and the host read it (no GPU,
+// no Context), and pcg_flush_kernel on caller-supplied vectors ----
+extern "C" int psk_lab_pcg_stagger(int32_t *blocks, int32_t *ring) {
+    if (blocks) *blocks = psk::kPcgStagger;
+    if (ring) *ring = psk::kPcgDefer;
+    return PSK_OK;
+}
+
+extern "C" int psk_lab_pcg_staggers(const psk_csr *A, const psk_prec *M, int32_t *on) {
+    if (!A || !on) return psk::fail(PSK_ERR_ARG, "psk_lab_pcg_staggers: NULL argument");
+    *on = psk::pcg_staggers(A, M) ? 1 : 0;
+    return PSK_OK;
+}
+
+extern "C" int psk_lab_pcg_flush_schedule(int32_t S, int64_t nv, int64_t tile, int64_t k, int32_t in_spmv,
+                                          int32_t *blk, int64_t *first_last) {
+    using namespace psk;
+    if (S < 1 || nv < 1 || tile < 0 || tile >= nv || k < 0 || !blk || !first_last)
+        return fail(PSK_ERR_ARG, "psk_lab_pcg_flush_schedule: bad arguments");
+    *blk = pcg_block_of_tile(tile, nv, S);
+    const PcgPend pd = pcg_flush_pending(S, *blk, k, in_spmv != 0);
+    first_last[0] = pd.first;
+    first_last[1] = pd.last;
+    return PSK_OK;
+}
+
+extern "C" int psk_lab_pcg_flush(int64_t n, int64_t k, int32_t stag, double *x, const double *ring,
+                                 const double *alphas) {
+    using namespace psk;
+    if (n < 1 || k < 1 || !x || !ring || !alphas) return fail(PSK_ERR_ARG, "psk_lab_pcg_flush: bad arguments");
+    if (stag && kPcgStagger == 0) return fail(PSK_ERR_UNSUPPORTED, "psk_lab_pcg_flush: built without the staggered flush");
+    Context *c;
+    PSK_TRY(ctx(&c));
+    const size_t vec = ((size_t)n * 8 + 255) / 256 * 256, al = ((size_t)k * 8 + 255) / 256 * 256;
+    DevBuf buf;
+    PSK_TRY(buf.ensure((kPcgDefer + 1) * vec + al));
+    char *d = buf.as<char>();
+    double *dx = reinterpret_cast<double *>(d), *da = reinterpret_cast<double *>(d + (kPcgDefer + 1) * vec);
+    PRing pr;
+    for (int t = 0; t < kPcgDefer; ++t) pr.b[t] = reinterpret_cast<double *>(d + (size_t)(t + 1) * vec);
+    int rc = PSK_OK;
+    if (hipMemcpyAsync(dx, x, (size_t)n * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(da, alphas, (size_t)k * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        rc = fail(PSK_ERR_HIP, "psk_lab_pcg_flush: copy");
+    for (int t = 0; t < kPcgDefer && rc == PSK_OK; ++t)
+        if (hipMemcpyAsync(pr.b[t], ring + (size_t)t * (size_t)n, (size_t)n * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            rc = fail(PSK_ERR_HIP, "psk_lab_pcg_flush: copy");
+    if (rc == PSK_OK) rc = launch_pcg_flush(n, dx, pr, da, k, stag != 0, c->stream);
+    if (rc == PSK_OK && hipMemcpyAsync(x, dx, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        rc = fail(PSK_ERR_HIP, "psk_lab_pcg_flush: copy back");
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == PSK_OK) rc = fail(PSK_ERR_HIP, "psk_lab_pcg_flush: sync");
+    buf.release();
     return rc;
 }

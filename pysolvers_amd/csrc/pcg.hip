@@ -188,7 +188,9 @@ __global__ __launch_bounds__(kBlock) void pcg_update_kernel(
 
 // ---- K3: x += alpha p (deferred, above), convergence test, beta, p = u + beta p (one-shot, as K2) --
 // A breakdown leaves the updates of the iterations since the last flush pending (pcg_flush_kernel).
-template <int JAC>
+// STAG (pcg_state.hpp, the staggered flush): the in-loop SpMV launches flush x block by block, so K3 touches x
+// only on the iteration that ends the solve, where it catches up every row with its own block's pending range.
+template <int JAC, bool STAG>
 __global__ __launch_bounds__(kBlock) void pcg_direction_kernel(
     int64_t n, double *__restrict__ x, const double *__restrict__ r, PRing pr, const double *__restrict__ dinv,
     double ds, const double *__restrict__ pap, const double *__restrict__ rrur, int nparts, PcgState *st,
@@ -211,16 +213,22 @@ __global__ __launch_bounds__(kBlock) void pcg_direction_kernel(
     // over the launch's tiles (see K2)
     const int64_t tile = tile_base + tile_of_block(tm);
     const double *pcur = pr.b[k % kPcgDefer];
-    // NOT __restrict__: on a flush iteration pnext is p_{k+1-kPcgDefer}'s buffer, which the x catch-up
-    // below reads through pr.b first; the store to pnext must stay after those loads
+    // NOT __restrict__: on a uniform flush pnext is p_{k+1-kPcgDefer}'s buffer, which the x catch-up below reads
+    // through pr.b first; the store to pnext must stay after those loads. Staggered, pnext (still
+    // p_{k+1-kPcgDefer}, ring slot (k + 1) % kPcgDefer) is older than every pending iteration: a block's range
+    // starts at k - (kPcgStagger - 1) or later (pcg_flush_pending) and kPcgStagger < kPcgDefer, so no catch-up
+    // reads it; the order of the loads and the store is kept all the same
     double *pnext = pr.b[(k + 1) % kPcgDefer];
-    const int q = pcg_pending(k);
+    constexpr int S = kPcgStagger > 0 ? kPcgStagger : 1;
+    const PcgPend pd = STAG ? pcg_flush_pending(S, pcg_block_of_tile(tile, (n + kVecTile - 1) / kVecTile, S), k, false)
+                            : pcg_uniform_pending(k);
+    const int q = (int)(k - pd.first);   // < kPcgDefer
     double alpha, beta;
     if (!pcg_direction_scalars(n, x, pcur, pTAp, rr, ur, udk, tauNB, st, udr, hist, k, maxiter, fail_on_maxiter,
-                               alpha, beta, tile, &pr, alphas))
+                               alpha, beta, tile, &pr, alphas, pd))
         return;
-    const bool flush = q == kPcgDefer - 1 || k == maxiter - 1;
-    const bool x0 = k < kPcgDefer;   // no flush yet: x is the implicit x0 = 0 (never loaded)
+    const bool flush = (!STAG && q == kPcgDefer - 1) || k == maxiter - 1;
+    const bool x0 = pd.first == 0;   // the rows were never stored: x is the implicit x0 = 0 (never loaded)
     if (tile == 0 && threadIdx.x == 0) {
         alphas[k] = alpha;
         if (flush) st->x_written = 1;
@@ -262,16 +270,32 @@ __global__ __launch_bounds__(kBlock) void pcg_direction_kernel(
     } else if (i < n) {
         const double u0 = JAC == 2 ? ds * r[i] : JAC ? dinv[i] * r[i] : r[i];
         const double pi = pcur[i];
-        if (flush) x[i] = pcg_catch_up(x0 ? 0.0 : x[i], &pr, q, k, alphas, i) + alpha * pi;
+        if (flush) x[i] = pcg_catch_up(x0 ? 0.0 : x[i], &pr, pd.first, k, alphas, i) + alpha * pi;
         pnext[i] = u0 + beta * pi;
     }
 }
 
-// the x updates a breakdown at iteration k left pending: iterations k - q .. k - 1, q = pcg_pending(k)
+// the x updates a breakdown at iteration k left pending: the iterations pcg_flush_pending (STAG: of the row's
+// block) or pcg_uniform_pending names; rows with nothing pending keep the x they hold
+template <bool STAG>
 __global__ void pcg_flush_kernel(int64_t n, double *__restrict__ x, PRing pr, const double *__restrict__ alphas,
                                  int64_t k) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) x[i] = pcg_catch_up(k < kPcgDefer ? 0.0 : x[i], &pr, pcg_pending(k), k, alphas, i);
+    constexpr int S = kPcgStagger > 0 ? kPcgStagger : 1;
+    const PcgPend pd = STAG ? pcg_flush_pending(S, pcg_block_of_tile(i / kVecTile, (n + kVecTile - 1) / kVecTile, S), k,
+                                                false)
+                            : pcg_uniform_pending(k);
+    if (i < n && pd.first <= pd.last) x[i] = pcg_catch_up(pd.first == 0 ? 0.0 : x[i], &pr, pd.first, k, alphas, i);
+}
+
+// pcg_flush_kernel on the solver's stream (psk_pcg after a breakdown; the lab library's test entry point)
+int launch_pcg_flush(int64_t n, double *x, const PRing &pr, const double *alphas, int64_t k, bool stag, hipStream_t s) {
+    if (n <= 0) return PSK_OK;
+    const dim3 g((unsigned)((n + kBlock - 1) / kBlock));
+    if (stag && kPcgStagger > 0) hipLaunchKernelGGL(pcg_flush_kernel<true>, g, dim3(kBlock), 0, s, n, x, pr, alphas, k);
+    else hipLaunchKernelGGL(pcg_flush_kernel<false>, g, dim3(kBlock), 0, s, n, x, pr, alphas, k);
+    PSK_HIP(hipGetLastError());
+    return PSK_OK;
 }
 
 // ---- end of a solve: the state, the scan of the gridsum ticket counters (gridsum_counter_check_kernel's)
@@ -429,6 +453,11 @@ static int pcg_workspace(psk_csr *A, int64_t maxiter, bool gen, bool own_x, int 
     return PSK_OK;
 }
 
+// psk_pcg's choice of the staggered x flush for a solve of A with preconditioner M (the lab library asks too)
+bool pcg_staggers(const psk_csr *A, const psk_prec *M) {
+    return kPcgStagger > 0 && !prec_is_general(M) && !A->comm && A->n > 0 && spmv_flush_eligible(A);
+}
+
 static void set_msg(psk_result *res, const char *m) {
     std::snprintf(res->msg, sizeof(res->msg), "%s", m);
 }
@@ -478,6 +507,9 @@ extern "C" int psk_pcg(const psk_csr *Ac, const psk_prec *M, const double *b, do
     // SpMV (spmv.hip pcg_init_diag_kernel, [p.Ap, b.b, u.r] into part1); otherwise pcg_init_kernel over the
     // SpMV's 256-row tiles (the same bits for b.b and u.r), or the general path's init over 512-element tiles
     const bool init_diag = !gen && !sharded && (jac == 0 || jac == 2) && pcg_init_diag_eligible(A);
+    // the staggered x flush (pcg_state.hpp): unsharded Jacobi/identity solves whose in-loop SpMV is the pair-row
+    // diagonal kernel; every other path keeps the uniform flush in K3
+    const bool stag = pcg_staggers(A, M);
     const int64_t nsl = n > 0 ? (n + kBlock - 1) / kBlock : 1;
     GridSum gs0, gs2, gs3;
     if (!init_diag) PSK_TRY(gridsum_prepare(c, gen ? nv : nsl, 2, w.pinit, &gs0));
@@ -635,9 +667,12 @@ extern "C" int psk_pcg(const psk_csr *Ac, const psk_prec *M, const double *b, do
         }
         // a timed launch records its events in its own dispatch (kernel start / end)
         uint64_t seq1 = 0;
+        // staggered: launch k >= 1 also brings block k mod kPcgStagger of x up to date (launch_spmv sizes the role)
+        SpmvFlush fl{w.x, w.alphas, w.pr, k, nv, 0, 0, 0, 0};
         if (!(init_diag && k == 0) &&
             (rc = launch_spmv(A, kSpmvDot, pk, w.Ap, nullptr, nullptr, w.part1, &w.st->done, s, timed ? ta[slot] : nullptr,
-                              timed ? tb[slot] : nullptr, 0, mbc ? &seq1 : nullptr)) != PSK_OK)
+                              timed ? tb[slot] : nullptr, 0, mbc ? &seq1 : nullptr, stag && k >= 1 ? &fl : nullptr)) !=
+                PSK_OK)
             break;
         // K2/K3 tiles in block order: XCD bands matching the SpMV's, and bands walked in alternating
         // directions (a serpentine over SpMV, K2, K3 meant to re-read Ap, r and p from the Infinity Cache),
@@ -680,18 +715,14 @@ extern "C" int psk_pcg(const psk_csr *Ac, const psk_prec *M, const double *b, do
                 if (t1 <= t0) return;
                 const dim3 g3((unsigned)(t1 - t0));
                 const TileMap tm3 = tile_map_for(t1 - t0, false);
-                if (jac == 2)
-                    hipLaunchKernelGGL(pcg_direction_kernel<2>, g3, dim3(kBlock), 0, s, n, w.x, w.r, w.pr, dinv, ds,
-                                       w.part1g, w.part2g, P, w.st, w.udr, w.hist, w.alphas, k, maxiter,
-                                       ctl->fail_on_maxiter, t0, tm3);
-                else if (jac == 1)
-                    hipLaunchKernelGGL(pcg_direction_kernel<1>, g3, dim3(kBlock), 0, s, n, w.x, w.r, w.pr, dinv, ds,
-                                       w.part1g, w.part2g, P, w.st, w.udr, w.hist, w.alphas, k, maxiter,
-                                       ctl->fail_on_maxiter, t0, tm3);
-                else
-                    hipLaunchKernelGGL(pcg_direction_kernel<0>, g3, dim3(kBlock), 0, s, n, w.x, w.r, w.pr, dinv, ds,
-                                       w.part1g, w.part2g, P, w.st, w.udr, w.hist, w.alphas, k, maxiter,
-                                       ctl->fail_on_maxiter, t0, tm3);
+#define PSK_PCG_K3(J, SG)                                                                                      \
+                hipLaunchKernelGGL((pcg_direction_kernel<J, SG>), g3, dim3(kBlock), 0, s, n, w.x, w.r, w.pr, dinv, ds, \
+                                   w.part1g, w.part2g, P, w.st, w.udr, w.hist, w.alphas, k, maxiter,               \
+                                   ctl->fail_on_maxiter, t0, tm3)
+                if (jac == 2) { if (stag) PSK_PCG_K3(2, (kPcgStagger > 0)); else PSK_PCG_K3(2, false); }
+                else if (jac == 1) { if (stag) PSK_PCG_K3(1, (kPcgStagger > 0)); else PSK_PCG_K3(1, false); }
+                else { if (stag) PSK_PCG_K3(0, (kPcgStagger > 0)); else PSK_PCG_K3(0, false); }
+#undef PSK_PCG_K3
             };
             if (overlap && k + 1 < maxiter) {
                 // the tiles holding the rows the neighbours need first, then their halo exchange on the
@@ -774,12 +805,22 @@ extern "C" int psk_pcg(const psk_csr *Ac, const psk_prec *M, const double *b, do
             bool x_written = hs.x_written != 0;
             // a dot(p,Ap) breakdown at k: the iterations since the last flush deferred their x updates
             bool more = !dev_io;   // work enqueued after the sync: the caller's x is ready only after another sync
-            if (!gen && hs.done == 2 && hs.brk_kind != 1 && pcg_pending(hs.iters) > 0 && n > 0) {
-                hipLaunchKernelGGL(pcg_flush_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n,
-                                   w.x, w.pr, w.alphas, (int64_t)hs.iters);
-                if (hipGetLastError() != hipSuccess) rc = fail(PSK_ERR_HIP, "pcg flush");
-                x_written = true;
-                more = true;   // also when an earlier flush had already stored x
+            // (staggered: every SpMV launch 1 .. k ran its flush role, so the schedule says per block what is
+            // stored and what is pending; uniform: one block)
+            if (!gen && hs.done == 2 && hs.brk_kind != 1 && n > 0) {
+                bool pending = false;
+                const int nblk = stag ? kPcgStagger : 1;
+                for (int b = 0; b < nblk; ++b) {
+                    if (stag && (int64_t)b * pcg_block_tiles(nv, kPcgStagger) >= nv) continue;   // owns no tile
+                    const PcgPend pd = stag ? pcg_flush_pending(kPcgStagger, b, hs.iters, false) : pcg_uniform_pending(hs.iters);
+                    pending = pending || pd.first <= pd.last;
+                    x_written = x_written || pd.first > 0;
+                }
+                if (pending) {
+                    rc = launch_pcg_flush(n, w.x, w.pr, w.alphas, (int64_t)hs.iters, stag, s);
+                    x_written = true;   // rows with nothing pending were stored by an earlier flush
+                    more = true;   // also when an earlier flush had already stored x
+                }
             }
             // no iteration stored x (b = 0, dot(u,r) = 0 at the start, maxiter = 0, or a dot(p,Ap)
             // breakdown at k = 0): the solution is x0 = 0

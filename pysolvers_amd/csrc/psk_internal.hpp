@@ -882,12 +882,14 @@ inline TileMap tile_map_for(int64_t ntiles, bool banded, bool rev = false) {
 inline TileMap tile_map_chunked(int64_t ntiles, int64_t c) {
     return c > 0 && ntiles >= 8 * c ? TileMap{0, 0, 0, c} : TileMap{0, 0, 0, 0};
 }
-__device__ __forceinline__ int64_t tile_of_block(TileMap tm) {
-    const int64_t b = blockIdx.x;
+// the tile of workgroup b of a launch of g (b = blockIdx.x of g = gridDim.x: tile_of_block; a launch that deals
+// workgroups of another role among the tile workgroups passes the index and count among the latter, keeping
+// b mod 8 = blockIdx.x mod 8)
+__device__ __forceinline__ int64_t tile_of_index(TileMap tm, int64_t b, int64_t g) {
     if (tm.c > 0) {   // b = 8 j + k on XCD k (round-robin dealing): its j-th tile is in chunk (j / c) * 8 + k
         const int64_t k = b & 7, j = b >> 3;
         const int64_t t = ((j / tm.c) * 8 + k) * tm.c + j % tm.c;
-        const int64_t full = (int64_t)(gridDim.x / (8 * tm.c)) * 8 * tm.c;
+        const int64_t full = (int64_t)(g / (8 * tm.c)) * 8 * tm.c;
         return b < full ? t : b;
     }
     if (tm.a == 0) return b;
@@ -895,6 +897,7 @@ __device__ __forceinline__ int64_t tile_of_block(TileMap tm) {
     const int64_t start = k * tm.a + (k < tm.r ? k : tm.r);
     return tm.rev ? start + (tm.a + (k < tm.r ? 1 : 0)) - 1 - j : start + j;
 }
+__device__ __forceinline__ int64_t tile_of_block(TileMap tm) { return tile_of_index(tm, blockIdx.x, gridDim.x); }
 
 // 16-byte vector accesses; *_nt = non-temporal (streamed data that is not re-read soon)
 typedef double dv2 __attribute__((ext_vector_type(2)));
@@ -993,8 +996,12 @@ void sliced_free(psk_csr *A);
 // ev0/ev1 (optional): HIP events the dispatch itself records at the kernel's start and end
 // (hipExtLaunchKernel), so their interval is the kernel alone, without the launch gaps around it
 // mail: the dot sum also goes to the communicator's next mailbox exchange (*mail_seq = its number)
+// flush: the launch also carries the PCG loop's x flush role (pcg_state.hpp; kSpmvDot on a matrix that is
+// spmv_flush_eligible only)
+struct SpmvFlush;
 int launch_spmv(const psk_csr *A, int mode, const double *x, double *y, const double *aux_d,
                 const double *aux_q, double *partial, const int32_t *done_flag, hipStream_t s,
-                hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int rev = 0, uint64_t *mail_seq = nullptr);
+                hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int rev = 0, uint64_t *mail_seq = nullptr,
+                const SpmvFlush *flush = nullptr);
 
 }  // namespace psk

@@ -842,14 +842,67 @@ __device__ __forceinline__ void diag_pair_fix(dv2 &v, const PairFix &f, const do
     }
 }
 
+// ---- the PCG loop's x flush as a second role of the in-loop launch (pcg_state.hpp: the staggered flush) ----
+// The launch of iteration k carries, beside its stencil workgroups, one flush workgroup per K3 tile of block
+// k mod S of x. A flush workgroup streams: it issues every load of its 512 rows (x unless still implicit, the
+// q <= S pending p's; 16-B, non-temporal, as K3's flush), consumes them in iteration order and stores x. It
+// draws no gridsum ticket, publishes nothing and exits at once when the solve has stopped. It reads x, p_{k-q}
+// .. p_{k-1} and alphas, none of which the stencil workgroups (x = p_k -> y = Ap) touch, and writes rows of x
+// no other workgroup of the launch owns.
+// Placement: workgroups are dealt in octets (8 consecutive blocks, one per XCD), an octet being all stencil or all
+// flush, so a stencil workgroup's index among the stencil workgroups keeps blockIdx.x mod 8 and the XCD bands of
+// the TileMap hold. The flush octets are dealt at a uniform ratio among the stencil octets (octet o is a flush
+// octet iff (o mul) >> 16 steps there): all of them first or all last measured 5-7% slower.
+// mul == 0 (a ratio the 16-bit step cannot express): the flush octets follow the stencil octets.
+// The flush octets among the launch's first o octets:
+__host__ __device__ inline uint32_t spmv_flush_octets_before(const SpmvFlush &f, uint32_t o) {
+    if (f.mul == 0) return o > f.ost ? o - f.ost : 0;
+    return (uint32_t)(((uint64_t)o * f.mul) >> 16);
+}
+__device__ __forceinline__ const SpmvFlush &spmv_flush_arg(const SpmvFlush &f) { return f; }
+
+template <int S>
+__device__ __forceinline__ void spmv_flush_tile(const SpmvFlush &fl, uint32_t f, int64_t n) {
+    const int64_t k = fl.k;
+    const int blk = (int)(k % S);
+    const PcgPend pd = pcg_flush_pending(S, blk, k, true);
+    const int q = (int)(k - pd.first);   // 1 .. S pending iterations
+    const bool x0 = pd.first == 0;       // never stored: the implicit x0 = 0
+    const int64_t i = ((int64_t)blk * pcg_block_tiles(fl.nv, S) + f) * kVecTile + 2 * threadIdx.x;
+    double *__restrict__ x = fl.x;
+    if (i + 1 < n) {
+        dv2 xo{0.0, 0.0};
+        if (!x0) xo = ld2nt(x + i);
+        dv2 pp[S];
+#pragma unroll
+        for (int t = 1; t <= S; ++t)
+            if (t <= q) pp[t - 1] = ld2nt(fl.pr.b[(k - t) % kPcgDefer] + i);
+#pragma unroll
+        for (int t = S; t >= 1; --t)
+            if (t <= q) {
+                const double a = fl.alphas[k - t];
+                xo.x = xo.x + a * pp[t - 1].x;           // x = x + alpha*p  (PCGSolver.py:121, iteration k-t)
+                xo.y = xo.y + a * pp[t - 1].y;
+            }
+        st2nt(x + i, xo);
+    } else if (i < n) {
+        x[i] = pcg_catch_up(x0 ? 0.0 : x[i], &fl.pr, pd.first, k, fl.alphas, i);
+    }
+}
+
 // 8 workgroups per CU (<= 64 VGPRs) where that does not spill: the H = 2 forms of the modes with aux loads keep
 // more in flight and are left at 4
-template <int MODE, int NB, int H>
+// FLUSH: empty, or one SpmvFlush — the launch then carries the flush role (kSpmvDot, H = 2 only; the other
+// instantiations' arguments and registers are those of the kernel without it)
+template <int MODE, int NB, int H, typename... FLUSH>
 __global__ __launch_bounds__(kBlock, (H == 2 && MODE != kSpmvPlain && MODE != kSpmvDot) ? 4 : 8) void spmv_diagp_kernel(
     int64_t n, const uint8_t *__restrict__ mask, DiagDesc dd, const double *__restrict__ x, double *__restrict__ y,
     const double *__restrict__ aux_d, const double *__restrict__ aux_q, GridSum gs, const int32_t *__restrict__ done,
-    TileMap tm, int64_t ntiles) {
+    TileMap tm, int64_t ntiles, FLUSH... flush) {
     constexpr int KM = 5;
+    constexpr bool FL = sizeof...(FLUSH) == 1;
+    static_assert(sizeof...(FLUSH) <= 1 && (!FL || (MODE == kSpmvDot && H == 2 && kPcgStagger > 0)),
+                  "the flush role rides on the PCG loop's launch only");
     static_assert(NB == 1 || NB == 2, "the 5-diagonal DPP orders");
     static_assert(H == 1 || H == 2, "half-slices per wave");
     constexpr int JD = NB == 1 ? 0 : 2, JM1 = NB == 1 ? 3 : 1, JP1 = NB == 1 ? 4 : 3;
@@ -860,7 +913,21 @@ __global__ __launch_bounds__(kBlock, (H == 2 && MODE != kSpmvPlain && MODE != kS
     const int32_t dnv = (done ? done : &g_spmv_never_done)[spmv_vzero()];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t grp = tile_of_block(tm);
+    int64_t sidx = blockIdx.x, scnt = gridDim.x;   // this workgroup's index among the stencil workgroups, their count
+    if constexpr (FL) {
+        const SpmvFlush &fl = spmv_flush_arg(flush...);
+        const uint32_t o = blockIdx.x >> 3, fb = spmv_flush_octets_before(fl, o);
+        if (spmv_flush_octets_before(fl, o + 1) != fb) {   // a flush octet
+            const uint32_t f = fb * 8 + (blockIdx.x & 7);
+            if (f >= fl.nfl || __builtin_amdgcn_readfirstlane(dnv) != 0) return;   // no tile, or the solve has stopped
+            spmv_flush_tile<kPcgStagger>(fl, f, n);
+            return;
+        }
+        sidx = (int64_t)(o - fb) * 8 + (blockIdx.x & 7);
+        scnt = (gs.nt + TPB - 1) / TPB;
+        if (sidx >= scnt) return;   // the last stencil octet's spare workgroups
+    }
+    const int64_t grp = tile_of_index(tm, sidx, scnt);
     const int64_t t = grp * TPB + (H == 2 ? wave : wave >> 1);   // this wave's slice
     const bool tv = t < ntiles;                                   // wave-uniform
     const int64_t tl = tv ? t : ntiles - 1;
@@ -925,7 +992,15 @@ __global__ __launch_bounds__(kBlock, (H == 2 && MODE != kSpmvPlain && MODE != kS
         if (threadIdx.x < TPB) gsl[threadIdx.x].cnt = 0;
         __syncthreads();
     }
-    if (pub && threadIdx.x == 0 && blockIdx.x == 0 && (gs.nt + TPB - 1) / TPB != gridDim.x) atomicOr(gs.err, 2);
+    if constexpr (FL) {   // the grid against the prepared one: the stencil octets only
+        const SpmvFlush &fl = spmv_flush_arg(flush...);
+        const uint32_t ot = gridDim.x >> 3;
+        if (pub && threadIdx.x == 0 && sidx == 0 &&
+            ((gridDim.x & 7) != 0 || (scnt + 7) / 8 != (int64_t)(ot - spmv_flush_octets_before(fl, ot))))
+            atomicOr(gs.err, 2);
+    } else {
+        if (pub && threadIdx.x == 0 && blockIdx.x == 0 && (gs.nt + TPB - 1) / TPB != gridDim.x) atomicOr(gs.err, 2);
+    }
     // the rare pairs that are not one 16-B load, then (DInv*q)[c] products (JX), all after every load was issued
 #pragma unroll
     for (int h = 0; h < H; ++h)
@@ -1751,11 +1826,39 @@ static int spmv_tpw() { return 2; }
 
 static int64_t spmv_tiles(const psk_csr *A) { return (A->n + A->tile_rows - 1) / A->tile_rows; }
 
+// sizes the flush role of launch fl.k (fl.k, fl.nv set) beside nwgp stencil workgroups: fl.nfl = the K3 tiles of
+// block k mod S (0: the block owns none), the octet counts and the interleave step; returns the launch's grid, a
+// multiple of 8 whose stencil octets are exactly those nwgp needs (0: too large for one launch)
+static uint32_t spmv_flush_grid(SpmvFlush &fl, int64_t nwgp) {
+    constexpr int S = kPcgStagger > 0 ? kPcgStagger : 1;
+    const int64_t per = pcg_block_tiles(fl.nv, S), t0 = (fl.k % S) * per;
+    const int64_t nf = std::min(fl.nv, t0 + per) - t0;
+    fl.nfl = nf > 0 ? (uint32_t)nf : 0;
+    if (fl.nfl == 0) return 0;
+    const int64_t ost = (nwgp + 7) / 8, ofl = (nf + 7) / 8;
+    if ((ost + ofl + 2) * 8 > (int64_t)INT32_MAX) return 0;
+    fl.ost = (uint32_t)ost;
+    fl.ofl = (uint32_t)ofl;
+    uint32_t ot = (uint32_t)(ost + ofl);
+    const int64_t mul = (ofl * 65536 + ot - 1) / ot;   // >= ofl / ot, so the first ost + ofl octets hold ofl
+    fl.mul = (uint32_t)std::min<int64_t>(std::max<int64_t>(mul, 1), 65535);
+    while (ot < (uint32_t)(ost + ofl + 2) * 2 &&
+           (spmv_flush_octets_before(fl, ot) < fl.ofl || ot - spmv_flush_octets_before(fl, ot) < fl.ost))
+        ++ot;   // at most one stencil octet joins per step: the loop stops at exactly ost of them
+    if (spmv_flush_octets_before(fl, ot) < fl.ofl || ot - spmv_flush_octets_before(fl, ot) != fl.ost) {
+        fl.mul = 0;   // a ratio the 16-bit step cannot express: the flush octets after the stencil octets
+        ot = (uint32_t)(ost + ofl);
+    }
+    return ot * 8;
+}
+
 int launch_spmv(const psk_csr *A, int mode, const double *x, double *y, const double *aux_d,
                 const double *aux_q, double *partial, const int32_t *done_flag, hipStream_t s, hipEvent_t ev0,
-                hipEvent_t ev1, int rev, uint64_t *mail_seq) {
+                hipEvent_t ev1, int rev, uint64_t *mail_seq, const SpmvFlush *flush) {
     Context *c;
     PSK_TRY(ctx(&c));
+    if (flush && (mode != kSpmvDot || !partial || !spmv_flush_eligible(A) || kPcgStagger == 0 || flush->k < 1))
+        return fail(PSK_ERR_ARG, "launch_spmv: the flush role needs the PCG loop's launch in the diagonal pair layout");
     const bool sliced = A->sl_off != nullptr || A->dg_mask != nullptr;   // 256-row slices
     const int64_t nwg = sliced ? (A->n + kSlice - 1) / kSlice : spmv_tiles(A);
     GridSum gs{nullptr, nullptr, nullptr, nullptr, 0, 0, -1, nullptr, nullptr, 0, 0};
@@ -1774,8 +1877,9 @@ int launch_spmv(const psk_csr *A, int mode, const double *x, double *y, const do
     }
     dim3 gd((unsigned)nwg), bd(kBlock);
     // XCD bands for the sliced layouts (N = 10M in the loop 0.078 -> 0.072 ms, back to back 0.067 ->
-    // 0.057 ms); the CSR tile kernel measured 2-3% slower with them (3163^2 and 16384^2), so it keeps
-    // block order
+    // 0.057 ms); the CSR tile kernel measured 2-3% slower with whole bands (3163^2 and 16384^2): it takes the
+    // chunked map instead, chunks of spmv_csr_chunk() consecutive tiles dealt over the XCDs (tile_map_chunked
+    // below; profiles/r6_csr_tilemap_ab.txt)
     // rev: each XCD walks its band backwards (the PCG loop alternates directions, PSK_K23_BANDS=2)
     TileMap tm = tile_map_for(nwg, sliced && spmv_xcd_bands(), rev != 0);
     if (!sliced && spmv_csr_chunk() > 0) tm = tile_map_chunked(nwg, spmv_csr_chunk());
@@ -1803,6 +1907,26 @@ int launch_spmv(const psk_csr *A, int mode, const double *x, double *y, const do
         const int64_t nwgp = pairh ? (nwg + (pairh == 2 ? 4 : 2) - 1) / (pairh == 2 ? 4 : 2) : 1;
         const dim3 gdp((unsigned)nwgp);
         const TileMap tmp = tile_map_for(nwgp, spmv_xcd_bands(), rev != 0);
+        // the PCG loop's launch with the flush role (pcg_state.hpp): one flush workgroup per K3 tile of block
+        // k mod kPcgStagger, dealt among the stencil workgroups (spmv_flush_grid); a block that owns no tile
+        // launches the kernel without the role
+#if PSK_PCG_STAGGER_ON
+        if (flush) {
+            SpmvFlush fl = *flush;
+            const uint32_t grid = spmv_flush_grid(fl, nwgp);
+            if (fl.nfl > 0) {
+                if (grid == 0) return fail(PSK_ERR_UNSUPPORTED, "launch_spmv: grid too large for the flush role");
+                if (nbk == 1)
+                    hipExtLaunchKernelGGL((spmv_diagp_kernel<kSpmvDot, 1, 2, SpmvFlush>), dim3(grid), bd, 0, s, ev0,
+                                          ev1, 0, A->n, A->dg_mask, dd, x, y, aux_d, aux_q, gs, done_flag, tmp, nwg, fl);
+                else
+                    hipExtLaunchKernelGGL((spmv_diagp_kernel<kSpmvDot, 2, 2, SpmvFlush>), dim3(grid), bd, 0, s, ev0,
+                                          ev1, 0, A->n, A->dg_mask, dd, x, y, aux_d, aux_q, gs, done_flag, tmp, nwg, fl);
+                PSK_HIP(hipGetLastError());
+                return PSK_OK;
+            }
+        }
+#endif
 #define PSK_DIAGP(M, NB, H)                                                                                        \
     hipExtLaunchKernelGGL((spmv_diagp_kernel<M, NB, H>), gdp, bd, 0, s, ev0, ev1, 0, A->n, A->dg_mask, dd, x, y, aux_d, \
                           aux_q, gs, done_flag, tmp, nwg)
@@ -1941,6 +2065,10 @@ static int diag_nb(const psk_csr *A) {
 }
 
 bool pcg_init_diag_eligible(const psk_csr *A) { return !A->comm && A->n > 0 && diag_nb(A) != 0; }
+// launch_spmv's choice of spmv_diagp_kernel<kSpmvDot, NB, 2>, unsharded
+bool spmv_flush_eligible(const psk_csr *A) {
+    return !A->comm && diag_nb(A) != 0 && A->n >= 2 && A->ncols >= 2 && diag_pair_h() == 2;
+}
 
 int launch_pcg_init_diag(const psk_csr *A, const double *b, double xs, double *p, double *Ap, double *out3,
                          const PcgInitFin &fin, hipStream_t s) {

@@ -9,7 +9,7 @@ OUT=gpurun_out; TAG=${TAG:-r2}
 mkdir -p $OUT
 export TMPDIR=/tmp
 sha256sum pysolvers_amd/_lib/libpsk.so > $OUT/pmc_${TAG}_lib.sha256
-ARGS=${PMC_ARGS:---steps 20 --warmup 2 --repeats 1 --cpu-iters 0 --spmv10m 0 --config1 0 --config2 0 --config4 0 --general 0}
+ARGS=${PMC_ARGS:---steps 20 --warmup 2 --repeats 1 --cpu-iters 0 --config1 0 --config2 0 --config4 0 --general 0}
 for S in ${SIDES:-16384 3163}; do
   for C in FETCH_SIZE WRITE_SIZE; do
     echo "== pmc side $S $C"
