@@ -9,7 +9,7 @@
 //  * cheby_setup_kernel + cheby_max_kernel: DInv (as jacobi_dinv_kernel) and the Gershgorin bound of D^-1 A in one
 //    pass over A at creation.
 //  * cheby_first_kernel: step 0, elementwise.
-//  * cheby_step_kernel: steps k >= 1, ONE launch each — the CSR SpMV's tile schedule (spmv.hip: a workgroup per
+//  * cheby_step_kernel: steps k >= 1, ONE launch each — the CSR SpMV's tile schedule (spmv_csr.hip: a workgroup per
 //    tile of rows, the tile's colidx/vals streamed non-temporally, rounded products staged through LDS, each lane
 //    summing its own row in stored order from 0.0) with the whole update in the epilogue. The row's v, DInv, d
 //    and z_in loads are issued before the reduction (their latency hides behind it), the d and z_out stores come
@@ -43,7 +43,7 @@ void cheby_free(Chebyshev *ch) {
     delete ch;
 }
 
-// the step kernel's tiles in chunks of consecutive tiles per XCD, as the CSR SpMV's (spmv.hip, PSK_CSR_CHUNK)
+// the step kernel's tiles in chunks of consecutive tiles per XCD, as the CSR SpMV's (spmv_csr.hip, kCsrChunk)
 constexpr int64_t kChebyChunk = 128;
 
 __device__ __forceinline__ int32_t ld_stream(const int32_t *p) { return __builtin_nontemporal_load(p); }

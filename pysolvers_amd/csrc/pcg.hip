@@ -1,7 +1,7 @@
 // pcg.hip — device-resident preconditioned CG (PCGSolver.solve, PCGSolver.py:64-142).
 //
 // Per iteration k three launches, no host synchronisation:
-//   K1  Ap = A p  and p.Ap                                         (spmv.hip, kSpmvDot)   :111,:113
+//   K1  Ap = A p  and p.Ap                                         (launch_spmv, kSpmvDot) :111,:113
 //   K2  alpha = uDotR/pTAp; r -= alpha Ap; u = M^-1 r; r.r and u.r   :114-125,:134
 //   K3  x += alpha p (alpha recomputed from K1's sum); ||r|| test (tau*||b||, or
 //       k==maxiter-1 when !failOnMaxiter); beta; p = u + beta p       :121,:125-138
@@ -34,7 +34,7 @@ namespace psk {
 // not stored either (round 5): K2 of iteration 0 reads b where it would read r, and writes r. 16 B/row.
 // Round 5: the sums run over the SpMV's 256-row gridsum tiles with one row per lane (two tiles per
 // workgroup) and the SpMV's tile epilogue (per-row products, wave totals in wave order): the diagonal
-// layout's init fused into the first SpMV (spmv.hip pcg_init_diag_kernel) then has the same bits.
+// layout's init fused into the first SpMV (spmv_diag.hip pcg_init_diag_kernel) then has the same bits.
 template <int JAC, bool FUSED>
 __global__ __launch_bounds__(kBlock) void pcg_init_kernel(int64_t n, const double *__restrict__ b,
                                                           const double *__restrict__ dinv, double ds,
@@ -504,7 +504,7 @@ extern "C" int psk_pcg(const psk_csr *Ac, const psk_prec *M, const double *b, do
     const int64_t nv = n > 0 ? (n + kVecTile - 1) / kVecTile : 1;
     if (nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_pcg: vector too long for a one-shot grid");
     // the init: unsharded with the diagonal layout (5 diagonals, one DInv value or none) fused into the first
-    // SpMV (spmv.hip pcg_init_diag_kernel, [p.Ap, b.b, u.r] into part1); otherwise pcg_init_kernel over the
+    // SpMV (spmv_diag.hip pcg_init_diag_kernel, [p.Ap, b.b, u.r] into part1); otherwise pcg_init_kernel over the
     // SpMV's 256-row tiles (the same bits for b.b and u.r), or the general path's init over 512-element tiles
     const bool init_diag = !gen && !sharded && (jac == 0 || jac == 2) && pcg_init_diag_eligible(A);
     // the staggered x flush (pcg_state.hpp): unsharded Jacobi/identity solves whose in-loop SpMV is the pair-row

@@ -1,5 +1,6 @@
 // pcg_state.hpp — the PCG solver state and the K3 scalar logic (PCGSolver.py:113-138), shared by pcg.hip
-// (the loop, K0/K2/K3) and spmv.hip (the PCG init fused into the first SpMV of the diagonal layout).
+// (the loop, K0/K2/K3) and spmv_diag.hip (the PCG init fused into the first SpMV of the diagonal layout, the
+// flush role of the in-loop SpMV).
 #pragma once
 #include "psk_internal.hpp"
 
@@ -101,7 +102,7 @@ struct PRing {
 __host__ __device__ inline int pcg_pending(int64_t k) { return (int)(k % kPcgDefer); }
 
 // The staggered flush (unsharded Jacobi/identity solves in the diagonal pair layout): the flush leaves K3 and
-// runs, a block of rows at a time, as extra streaming workgroups of the in-loop SpMV launches (spmv.hip, the
+// runs, a block of rows at a time, as extra streaming workgroups of the in-loop SpMV launches (spmv_diag.hip, the
 // flush role of spmv_diagp_kernel). The rows are cut into S contiguous blocks on K3-tile boundaries; SpMV launch
 // k >= 1 brings block k mod S up to date, i.e. applies every pending update of iterations < k in iteration order.
 // Whoever ends the solve (K3 on convergence or at maxiter - 1, pcg_flush_kernel after a breakdown) catches up
@@ -198,11 +199,11 @@ __device__ inline bool pcg_direction_scalars(int64_t n, double *__restrict__ x, 
     return true;
 }
 
-// the PCG init fused into the first SpMV (spmv.hip, pcg_init_diag_kernel): the diagonal layout in the
+// the PCG init fused into the first SpMV (spmv_diag.hip, pcg_init_diag_kernel): the diagonal layout in the
 // 5-diagonal DPP order, unsharded; xs = the one DInv value (Jacobi) or 1.0 (none). [p_0.Ap_0, b.b, u.r] into
 // out3[0..2], p_0 into p, Ap_0 into Ap; fin runs on sums 1 and 2 (fin.off = 1)
 bool pcg_init_diag_eligible(const psk_csr *A);
-// the in-loop SpMV of this matrix is the pair-row diagonal kernel that carries the flush role (spmv.hip)
+// the in-loop SpMV of this matrix is the pair-row diagonal kernel that carries the flush role (spmv_diag.hip)
 bool spmv_flush_eligible(const psk_csr *A);
 // psk_pcg takes the staggered flush for this matrix and preconditioner (nullptr: none)
 bool pcg_staggers(const psk_csr *A, const psk_prec *M);

@@ -175,7 +175,7 @@ struct psk_csr {
     int32_t *colidx = nullptr;
     double *vals = nullptr;
     int device = 0;
-    // sliced copy of the same entries (spmv.hip, "sliced layout"): slices of kSlice rows, slot-major
+    // sliced copy of the same entries (spmv_sliced.hip, "sliced layout"): slices of kSlice rows, slot-major
     // inside a slice (values in slot pairs, or byte indices into sl_dict), per slice either packed
     // int16 column-delta pairs (sl_fmt[t] = 1) or int32 columns (sl_col); sl_col and sl_val are
     // addressed from the slice's slot offset sl_off[t], the word stream sl_pcol (packed columns,
@@ -191,9 +191,9 @@ struct psk_csr {
     int32_t sl_dict_n = 0;
     int32_t sl_uniform_w = 0;    // > 0: every slice this wide and packed (offsets computed, not loaded)
     int32_t sl_compact = 0;      // uniform, odd width, <= 2 dictionary values: the value-index bits sit in
-                                 // the last delta word's free half (no index words; spmv_uniform_kernel CMP)
+                                 // the last delta word's free half (no index words; spmv_uniform_multi_kernel)
     int64_t sl_slots = 0, sl_packed_slots = 0, sl_stream_bytes = 0;
-    // diagonal layout (spmv.hip, "diagonal layout"; round 5): every row's entries lie, in stored order, on
+    // diagonal layout (spmv_diag.hip, "diagonal layout"; round 5): every row's entries lie, in stored order, on
     // a subsequence of dg_K <= 8 diagonals c = row + dg_d[j] (columns outside [0, n) of a row-block shard
     // mapped to its halo by dg_lo / dg_hi) with ONE value dg_v[j] per diagonal; per row a presence mask
     // byte (dg_mask, padded to whole 256-row slices). Present instead of the sliced copy when it applies.
@@ -991,7 +991,6 @@ int tile_rows_for(int64_t n, int64_t nnz);
 // SpMV layout of a freshly created matrix: the sliced copy when it streams no more bytes than the
 // CSR arrays (PSK_SPMV_LAYOUT=csr|sliced overrides); called at the end of every creation path
 int csr_choose_layout(psk_csr *A, hipStream_t s);
-void sliced_free(psk_csr *A);
 // one-shot SpMV (grid = tiles of A->tile_rows rows); dot modes write their grid sum to partial[0].
 // ev0/ev1 (optional): HIP events the dispatch itself records at the kernel's start and end
 // (hipExtLaunchKernel), so their interval is the kernel alone, without the launch gaps around it

@@ -8,9 +8,9 @@ cd "$(dirname "$0")/.."
 B=tools/bin/asan; mkdir -p $B /tmp/asan_obj
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer -Xarch_host -fno-sanitize-recover=undefined"
 pids=()
-for f in runtime spmv pcg gmres dist shmcomm ilu amg mmio; do
+for f in $(make -s -C pysolvers_amd/csrc print-srcs); do   # the Makefile's list of libpsk's sources
   /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -w $SAN \
-      -c pysolvers_amd/csrc/$f.hip -o /tmp/asan_obj/$f.o &
+      -c pysolvers_amd/csrc/$f -o /tmp/asan_obj/${f%.hip}.o &
   pids+=($!)
 done
 for p in "${pids[@]}"; do wait $p; done

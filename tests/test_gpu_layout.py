@@ -351,7 +351,7 @@ def test_diag_layout_refused(psk):
 
 @pytest.mark.parametrize("prec", ["jacobi", "identity"])
 def test_pcg_init_edges_diag_vs_csr(psk, prec, monkeypatch):
-    """The PCG init fused into the first SpMV (diagonal layout, spmv.hip pcg_init_diag_kernel) against
+    """The PCG init fused into the first SpMV (diagonal layout, spmv_diag.hip pcg_init_diag_kernel) against
     pcg_init_kernel + the CSR SpMV, at the init's edges: b = 0 (PCGSolver.py:87-88, converged before any
     iteration), maxiter 0, 1 and 2 (the loop stops before, at and right after the fused launch's first
     consumer), a 1-line grid and a grid smaller than one 256-row tile: identical status, x and history."""

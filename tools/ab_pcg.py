@@ -2,7 +2,7 @@
 """Same-box A/B of libpsk variants on the bench's PCG+Jacobi systems (lab tool, not the bench).
 
     python tools/ab_pcg.py --sides 3163,16384 --rounds 2 \
-        base= tpw2=PSK_SPMV_TPW=2 k3pnt=@tools/bin/ab_k3pnt/libpsk.so
+        base= csr=PSK_SPMV_LAYOUT=csr k3pnt=@tools/bin/ab_k3pnt/libpsk.so
 
 Each VARIANT is NAME=[@LIBPATH][,ENV=VALUE...]; every (round, variant) runs in a fresh process (the
 library reads its switches once), interleaved, and prints one JSON line per run: PCG it/s (median of
