@@ -129,6 +129,8 @@ LAB_SIGNATURES = {
     "psk_lab_pcg_staggers": (ctypes.c_int, [P, P, ctypes.POINTER(I32)]),
     "psk_lab_pcg_flush_schedule": (ctypes.c_int, [I32, I64, I64, I64, I32, ctypes.POINTER(I32), ctypes.POINTER(I64)]),
     "psk_lab_pcg_flush": (ctypes.c_int, [I64, I64, I32, P, P, P]),
+    "psk_lab_solver_layout": (ctypes.c_int, [I32, I64, I64, I64, I64, I32, I32, ctypes.POINTER(I64),
+                                            ctypes.POINTER(I32), ctypes.POINTER(I64)]),
 }
 _lab = None
 

@@ -18,6 +18,7 @@
 // Reference defects: self.precond never set (:71) -> we always form M;
 // NameError at maxiter (:180) -> we return the MAXITER status handleMaxiter would have built.
 #include "psk_internal.hpp"
+#include "solve_loop.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -229,7 +230,44 @@ static bool small_solve(int m, const double *Rcm, int ld, const double *rhs, std
     return true;
 }
 
-static inline size_t aup(size_t v) { return (v + 255) / 256 * 256; }
+// K: the Krylov basis of one cycle (restart, or maxiter when it is 0), at most maxiter, at least 1
+static int64_t gm_basis(int64_t maxiter, int64_t restart) {
+    const int64_t K = restart > 0 && restart < maxiter ? restart : maxiter;
+    return K < 1 ? 1 : K;
+}
+
+struct GmresWork {
+    double *Q, *u, *x, *bv, *w, *tt;   // w, tt: general (ILU) preconditioner only (M^-1 q_k, scratch)
+    GmresState *st;
+    double *H, *R, *CS, *g, *pa, *dhist, *dy, *hv;
+};
+// the layout of A->ws (big) and A->ws_small (sm): run on null-based carvers for the sizes, then on the buffers
+static void gm_layout(Carve &big, Carve &sm, int64_t n, int64_t maxiter, int64_t K, bool gen, GmresWork &w) {
+    const size_t vec = (size_t)n * 8, ld = (size_t)K + 1;
+    w.Q = big.take<double>(((vec + 255) / 256 * 256) * ld);
+    w.u = big.take<double>(vec);
+    w.x = big.take<double>(vec);
+    w.bv = big.take<double>(vec);
+    w.w = gen ? big.take<double>(vec) : nullptr;
+    w.tt = gen ? big.take<double>(vec) : nullptr;
+    w.st = sm.take<GmresState>(sizeof(GmresState));
+    w.H = sm.take<double>(ld * K * 8);
+    w.R = sm.take<double>(ld * K * 8);
+    w.CS = sm.take<double>((size_t)2 * K * 8);
+    w.g = sm.take<double>(ld * 8);
+    w.pa = sm.take<double>((size_t)kMaxGrid * 8);   // partials of the cycle-start norm / the residual's sum
+    w.dhist = sm.take<double>((size_t)(maxiter + 1) * 8);
+    w.dy = sm.take<double>(ld * 8);
+    w.hv = sm.take<double>((size_t)(K + 2) * 8);    // K + 2 grid sums of a step (gm_mgs_kernel)
+}
+void gmres_layout_probe(int64_t n, int64_t maxiter, int64_t restart, bool gen, std::vector<int64_t> *log, int64_t *bytes) {
+    Carve big, sm;
+    big.log = sm.log = log;
+    GmresWork w;
+    gm_layout(big, sm, n, maxiter, gm_basis(maxiter, restart), gen, w);
+    bytes[0] = (int64_t)big.off;
+    bytes[1] = (int64_t)sm.off;
+}
 
 }  // namespace psk
 
@@ -250,16 +288,14 @@ extern "C" int psk_gmres(const psk_csr *Ac, const psk_prec *M, const double *b, 
     hipStream_t s = c->stream;
     std::memset(res, 0, sizeof(*res));
     const int64_t n = A->n, maxiter = ctl->maxiter;
-    int64_t K = ctl->restart > 0 ? ctl->restart : maxiter;
-    if (K > maxiter) K = maxiter;
-    if (K < 1) K = 1;
+    const int64_t K = gm_basis(maxiter, ctl->restart);
     const int ld = (int)(K + 1);
     const double *dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
     const int gs = 1;   // partials of a dot-mode SpMV: it finishes its sum in-launch (gridsum)
     const int gv = grid_for_rows(c, n, kVecTile);
     const int64_t nv = n > 0 ? (n + kVecTile - 1) / kVecTile : 1;   // one-shot grid of the MGS kernels
     if (nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_gmres: vector too long for a one-shot grid");
-    const size_t vec = aup((size_t)n * 8);
+    const size_t vec = ((size_t)n * 8 + 255) / 256 * 256;
     const size_t qbytes = vec * (size_t)(K + 1);
     {
         size_t fr = 0, tot = 0;
@@ -269,37 +305,17 @@ extern "C" int psk_gmres(const psk_csr *Ac, const psk_prec *M, const double *b, 
     }
     // general (ILU) preconditioner: M^-1 q_k is materialised in w before the SpMV; t is scratch
     const bool gen = prec_is_general(M);
-    PSK_TRY(A->ws.ensure(qbytes + (gen ? 5 : 3) * vec));
-    char *wb = A->ws.as<char>();
-    double *Q = reinterpret_cast<double *>(wb);
-    double *u = reinterpret_cast<double *>(wb + qbytes);
-    double *x = reinterpret_cast<double *>(wb + qbytes + vec);
-    double *bv = reinterpret_cast<double *>(wb + qbytes + 2 * vec);
-    double *w = gen ? reinterpret_cast<double *>(wb + qbytes + 3 * vec) : nullptr;
-    double *tt = gen ? reinterpret_cast<double *>(wb + qbytes + 4 * vec) : nullptr;
-    const size_t hb = aup((size_t)ld * K * 8);
-    const size_t small = aup(sizeof(GmresState)) + 2 * hb + aup((size_t)2 * K * 8) + aup((size_t)ld * 8) +
-                         aup((size_t)kMaxGrid * 8) + aup((size_t)(maxiter + 1) * 8) + aup((size_t)ld * 8) +
-                         aup((size_t)(K + 2) * 8);
-    PSK_TRY(A->ws_small.ensure(small));
-    char *sb = A->ws_small.as<char>();
-    GmresState *st = reinterpret_cast<GmresState *>(sb);
-    sb += aup(sizeof(GmresState));
-    double *H = reinterpret_cast<double *>(sb);
-    sb += hb;
-    double *R = reinterpret_cast<double *>(sb);
-    sb += hb;
-    double *CS = reinterpret_cast<double *>(sb);
-    sb += aup((size_t)2 * K * 8);
-    double *g = reinterpret_cast<double *>(sb);
-    sb += aup((size_t)ld * 8);
-    double *pa = reinterpret_cast<double *>(sb);   // partials of the cycle-start norm / the residual's sum
-    sb += aup((size_t)kMaxGrid * 8);
-    double *dhist = reinterpret_cast<double *>(sb);
-    sb += aup((size_t)(maxiter + 1) * 8);
-    double *dy = reinterpret_cast<double *>(sb);
-    sb += aup((size_t)ld * 8);
-    double *hv = reinterpret_cast<double *>(sb);   // K + 2 grid sums of a step (gm_mgs_kernel)
+    int64_t need[2];
+    gmres_layout_probe(n, maxiter, ctl->restart, gen, nullptr, need);
+    PSK_TRY(A->ws.ensure((size_t)need[0]));
+    PSK_TRY(A->ws_small.ensure((size_t)need[1]));
+    Carve big{A->ws.as<char>()}, sm{A->ws_small.as<char>()};
+    GmresWork gw;
+    gm_layout(big, sm, n, maxiter, K, gen, gw);
+    double *Q = gw.Q, *u = gw.u, *x = gw.x, *bv = gw.bv, *w = gw.w, *tt = gw.tt, *H = gw.H, *R = gw.R, *CS = gw.CS,
+           *g = gw.g, *pa = gw.pa, *dhist = gw.dhist, *dy = gw.dy, *hv = gw.hv;
+    GmresState *st = gw.st;
+    const size_t hb = ((size_t)ld * K * 8 + 255) / 256 * 256;
 
     // events and the poll words come from the device's SolveKit (allocated once, round 4)
     SolveKit *kit;

@@ -339,3 +339,21 @@ extern "C" int psk_lab_pcg_flush(int64_t n, int64_t k, int32_t stag, double *x, 
     buf.release();
     return rc;
 }
+
+// ---- the solvers' workspace layouts (solve_loop.hpp Carve) on null-based carvers: no GPU, no Context ----
+extern "C" int psk_lab_solver_layout(int32_t solver, int64_t n, int64_t ncols, int64_t maxiter, int64_t restart,
+                                     int32_t flags, int32_t P, int64_t *offsets, int32_t *count, int64_t *bytes) {
+    using namespace psk;
+    if (n < 0 || ncols < 0 || maxiter < 0 || restart < 0 || P < 1 || !offsets || !count || !bytes)
+        return fail(PSK_ERR_ARG, "psk_lab_solver_layout: bad arguments");
+    std::vector<int64_t> log;
+    const bool gen = (flags & PSK_LAB_LAYOUT_GEN) != 0;
+    if (solver == PSK_LAB_SOLVER_PCG) pcg_layout_probe(n, ncols, maxiter, gen, (flags & PSK_LAB_LAYOUT_OWN_X) != 0, P, &log, bytes);
+    else if (solver == PSK_LAB_SOLVER_GMRES) gmres_layout_probe(n, maxiter, restart, gen, &log, bytes);
+    else if (solver == PSK_LAB_SOLVER_VCYCLE) vcycle_layout_probe(n, maxiter, (flags & PSK_LAB_LAYOUT_DEV_IO) != 0, &log, bytes);
+    else return fail(PSK_ERR_ARG, "psk_lab_solver_layout: unknown solver");
+    if ((size_t)*count < log.size()) return fail(PSK_ERR_ARG, "psk_lab_solver_layout: offsets too short");
+    *count = (int32_t)log.size();
+    for (size_t i = 0; i < log.size(); ++i) offsets[i] = log[i];
+    return PSK_OK;
+}

@@ -22,7 +22,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdio>
-
+#include <type_traits>
 
 namespace psk {
 
@@ -387,9 +387,7 @@ __global__ __launch_bounds__(kBlock) void pcg_gen_direction_kernel(
 }
 
 // -------------------------------------------------------------------------------------------------
-// host driver
-
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// host driver: psk_pcg = plan, init, the loop (one iteration a function of k), finish, report
 
 struct PcgWork {
     double *x, *r, *p, *Ap, *u, *part1, *part2, *part3, *udr, *hist;
@@ -402,54 +400,47 @@ struct PcgWork {
     PcgState *st;
 };
 
-static int pcg_workspace(psk_csr *A, int64_t maxiter, bool gen, bool own_x, int P, PcgWork &w) {
-    const size_t vec = align_up((size_t)A->n * 8, 256), vecc = align_up((size_t)A->ncols * 8, 256);
+// the layout of A->ws (big) and A->ws_small (sm): run on null-based carvers for the sizes, then on the buffers
+static void pcg_layout(Carve &big, Carve &sm, int64_t n, int64_t ncols, int64_t maxiter, bool gen, bool own_x, int P,
+                       PcgWork &w) {
+    const size_t vec = (size_t)n * 8, vecc = (size_t)ncols * 8, it = (size_t)(maxiter + 1) * 8;
+    w.r = big.take<double>(vec);
+    w.Ap = big.take<double>(vec);
     // x lives in the caller's device vector when the solve writes there directly (own_x false)
-    const size_t nx = own_x ? 1 : 0;
-    const size_t big = (2 + nx + (gen ? 1 : 0)) * vec + (gen ? 1 : kPcgDefer) * vecc;
-    PSK_TRY(A->ws.ensure(big > 0 ? big : 256));
-    char *b = A->ws.as<char>();
-    w.r = reinterpret_cast<double *>(b);
-    w.Ap = reinterpret_cast<double *>(b + vec);
-    w.x = own_x ? reinterpret_cast<double *>(b + 2 * vec) : nullptr;
-    char *pb = b + (2 + nx) * vec;
-    w.p = reinterpret_cast<double *>(pb);
-    w.u = gen ? reinterpret_cast<double *>(pb + vecc) : nullptr;
-    for (int t = 0; t < kPcgDefer; ++t)
-        w.pr.b[t] = gen ? (t == 0 ? w.p : nullptr) : reinterpret_cast<double *>(pb + t * vecc);
-    const size_t small = align_up(sizeof(PcgState), 256) + 2 * align_up(kMaxGrid * 8, 256) +
-                         align_up(2 * kMaxGrid * 8, 256) + align_up((size_t)(maxiter + 2) * 8, 256) +
-                         align_up((size_t)(maxiter + 1) * 8, 256) + align_up((size_t)(maxiter + 1) * 8, 256) + 256;
-    const size_t gath = P > 1 ? align_up((size_t)P * 8, 256) + 2 * align_up((size_t)P * 16, 256) : 0;
-    PSK_TRY(A->ws_small.ensure(small + gath));
-    char *s = A->ws_small.as<char>();
-    w.st = reinterpret_cast<PcgState *>(s);
-    s += align_up(sizeof(PcgState), 256);
-    w.part1 = reinterpret_cast<double *>(s);
-    s += align_up(kMaxGrid * 8, 256);
-    w.part3 = reinterpret_cast<double *>(s);
-    s += align_up(kMaxGrid * 8, 256);
-    w.part2 = reinterpret_cast<double *>(s);
-    s += align_up(2 * kMaxGrid * 8, 256);
-    w.udr = reinterpret_cast<double *>(s);
-    s += align_up((size_t)(maxiter + 2) * 8, 256);
-    w.hist = reinterpret_cast<double *>(s);
-    s += align_up((size_t)(maxiter + 1) * 8, 256);
-    w.alphas = reinterpret_cast<double *>(s);
-    s += align_up((size_t)(maxiter + 1) * 8, 256);
-    w.pinit = reinterpret_cast<double *>(s);
-    s += 256;
-    if (P > 1) {
-        w.part1g = reinterpret_cast<double *>(s);
-        s += align_up((size_t)P * 8, 256);
-        w.part2g = reinterpret_cast<double *>(s);
-        s += align_up((size_t)P * 16, 256);
-        w.initg = reinterpret_cast<double *>(s);
-    } else {
-        w.part1g = w.part1;
-        w.part2g = w.part2;
-        w.initg = w.pinit;
-    }
+    w.x = own_x ? big.take<double>(vec) : nullptr;
+    for (int t = 0; t < kPcgDefer; ++t) w.pr.b[t] = gen && t > 0 ? nullptr : big.take<double>(vecc);
+    w.p = w.pr.b[0];
+    w.u = gen ? big.take<double>(vec) : nullptr;
+    w.st = sm.take<PcgState>(sizeof(PcgState));
+    w.part1 = sm.take<double>(kMaxGrid * 8);
+    w.part3 = sm.take<double>(kMaxGrid * 8);
+    w.part2 = sm.take<double>(2 * kMaxGrid * 8);
+    w.udr = sm.take<double>(it + 8);
+    w.hist = sm.take<double>(it);
+    w.alphas = sm.take<double>(it);
+    w.pinit = sm.take<double>(256);
+    w.part1g = P > 1 ? sm.take<double>((size_t)P * 8) : w.part1;
+    w.part2g = P > 1 ? sm.take<double>((size_t)P * 16) : w.part2;
+    w.initg = P > 1 ? sm.take<double>((size_t)P * 16) : w.pinit;
+}
+
+void pcg_layout_probe(int64_t n, int64_t ncols, int64_t maxiter, bool gen, bool own_x, int P, std::vector<int64_t> *log,
+                      int64_t *bytes) {
+    Carve big, sm;
+    big.log = sm.log = log;
+    PcgWork w;
+    pcg_layout(big, sm, n, ncols, maxiter, gen, own_x, P, w);
+    bytes[0] = big.off > 0 ? (int64_t)big.off : 256;
+    bytes[1] = (int64_t)sm.off;
+}
+
+static int pcg_workspace(psk_csr *A, int64_t maxiter, bool gen, bool own_x, int P, PcgWork &w) {
+    int64_t need[2];
+    pcg_layout_probe(A->n, A->ncols, maxiter, gen, own_x, P, nullptr, need);
+    PSK_TRY(A->ws.ensure((size_t)need[0]));
+    PSK_TRY(A->ws_small.ensure((size_t)need[1]));
+    Carve big{A->ws.as<char>()}, sm{A->ws_small.as<char>()};
+    pcg_layout(big, sm, A->n, A->ncols, maxiter, gen, own_x, P, w);
     return PSK_OK;
 }
 
@@ -460,6 +451,428 @@ bool pcg_staggers(const psk_csr *A, const psk_prec *M) {
 
 static void set_msg(psk_result *res, const char *m) {
     std::snprintf(res->msg, sizeof(res->msg), "%s", m);
+}
+
+// every path of a solve, decided once (pcg_plan); the phases read it
+struct PcgPlan {
+    int64_t n, maxiter;
+    bool gen;             // general preconditioner (ILU): u = M^-1 r materialised between K2 and K3
+    bool sharded;         // P ranks, scalars gathered (not all-reduced) and summed in rank order on every rank
+    bool dev_io;          // b and x in HBM: read b in place, write x in place
+    int P, jac;           // jac: 0 none, 1 DInv streamed, 2 one DInv value ds
+    const double *dinv;
+    double ds;
+    // one-shot grid of K0/K2/K3 (one 512-element tile per workgroup); K0/K1/K2 finish their dot products
+    // in-launch (gridsum), so the loop's scalars are part1[0] = p.Ap and part2[0..1] = (r.r, u.r)
+    int64_t nv, nsl;      // nsl: the SpMV's 256-row gridsum tiles
+    // the init: unsharded with the diagonal layout (5 diagonals, one DInv value or none) fused into the first
+    // SpMV (spmv_diag.hip pcg_init_diag_kernel, [p.Ap, b.b, u.r] into part1); otherwise pcg_init_kernel over the
+    // SpMV's 256-row tiles (the same bits for b.b and u.r), or the general path's init over 512-element tiles
+    bool init_diag;
+    // the staggered x flush (pcg_state.hpp): unsharded Jacobi/identity solves whose in-loop SpMV is the pair-row
+    // diagonal kernel; every other path keeps the uniform flush in K3
+    bool stag;
+    // halo overlap (sharded, Jacobi/identity): when every row a neighbour needs lies in the first ov_lo
+    // or the last nv - ov_hi K3 tiles (row-block shards of a banded matrix: one grid line each side),
+    // those tiles run first and the exchange of p overlaps the remaining tiles of K3
+    bool overlap;
+    int64_t ov_lo, ov_hi;
+    int C;                // iterations per poll chunk
+    // sharded with a mailbox (psk_comm_mailbox): the ranks' scalars go kernel -> mailbox -> gather kernel
+    // instead of ncclAllGather; same gathered arrays, same rank-order sums
+    psk_comm *mbc;
+};
+
+static int pcg_plan(const psk_csr *A, const psk_prec *M, const psk_ctl *ctl, int32_t loc, PcgPlan &pl) {
+    pl.n = A->n;
+    pl.maxiter = ctl->maxiter;
+    pl.gen = prec_is_general(M);
+    if (pl.gen && A->comm) return fail(PSK_ERR_UNSUPPORTED, "psk_pcg: ILU preconditioning of a sharded matrix");
+    pl.sharded = A->comm != nullptr;
+    pl.P = pl.sharded ? A->comm->nranks : 1;
+    pl.dev_io = loc == PSK_DEVICE;
+    pl.dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
+    pl.jac = !pl.dinv ? 0 : M->dinv_uniform ? 2 : 1;
+    pl.ds = pl.jac == 2 ? M->dinv_value : 0.0;
+    pl.nv = pl.n > 0 ? (pl.n + kVecTile - 1) / kVecTile : 1;
+    if (pl.nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_pcg: vector too long for a one-shot grid");
+    pl.nsl = pl.n > 0 ? (pl.n + kBlock - 1) / kBlock : 1;
+    pl.init_diag = !pl.gen && !pl.sharded && (pl.jac == 0 || pl.jac == 2) && pcg_init_diag_eligible(A);
+    pl.stag = pcg_staggers(A, M);
+    pl.C = ctl->check_every > 0 ? ctl->check_every : (pl.n >= (1 << 20) ? 2 : 16);
+    // On by default (PSK_HALO_OVERLAP=0 turns it off); DESIGN.md §6 states the rule: the overlap moves
+    // no arithmetic (sharded histories are bit-identical either way) and takes the halo's latency off
+    // the critical path whenever K3's interior tiles outlast the exchange, which they do at every
+    // size the 8-GPU run uses (>= 1.25M rows per rank); an 8-GPU A/B of the driver's run decides it.
+    static const bool overlap_on = [] {
+        const char *e = std::getenv("PSK_HALO_OVERLAP");
+        return !(e && std::atoi(e) == 0);
+    }();
+    pl.ov_lo = 0;
+    pl.ov_hi = pl.nv;
+    pl.overlap = overlap_on && pl.sharded && !pl.gen && halo_split(A, kVecTile, pl.nv, pl.ov_lo, pl.ov_hi);
+    pl.mbc = pl.sharded && A->comm->mb ? A->comm : nullptr;
+    return PSK_OK;
+}
+
+// what the phases of one solve share
+struct PcgRun {
+    psk_csr *A;
+    const psk_prec *M;
+    const psk_ctl *ctl;
+    Context *c;
+    SolveKit *kit;
+    hipStream_t s, cs;            // cs: the halo exchanges of the overlap
+    PcgPlan pl;
+    PcgWork w;
+    GridSum gs2, gs3;
+    const double *bd;             // b on the device
+    bool halo_pending = false;    // an exchange on cs the next SpMV (or the end of the solve) waits for
+};
+
+// f(integral_constant<int, jac>, bool_constant<flag>): the <JAC, bool> forms of K0, K2 and K3
+template <class F> static void pcg_dispatch(int jac, bool flag, F &&f) {
+    auto on = [&](auto J) {
+        if (flag) f(J, std::true_type{});
+        else f(J, std::false_type{});
+    };
+    if (jac == 2) on(std::integral_constant<int, 2>{});
+    else if (jac == 1) on(std::integral_constant<int, 1>{});
+    else on(std::integral_constant<int, 0>{});
+}
+
+// Optional timing (ctl.time_kernels = S > 0): every S-th SpMV between two events of a ring of kTimedSlots
+// (sampled: an event pair costs ~5% of an iteration at N = 10M); sharded, the same iterations time this rank's
+// p.Ap gather and the halo exchange of the iteration (ABI 4: psk_result.gather_ms / halo_ms)
+struct PcgTimers {
+    SolveKit *kit;
+    int S;
+    bool skip0;   // init_diag: iteration 0's SpMV ran inside the init launch, not sampled
+    int64_t tk[kTimedSlots];                        // the iteration a slot holds (-1: free)
+    bool tgat[kTimedSlots], thalo[kTimedSlots];     // sharded: the slot's gather / halo events were recorded
+    std::vector<float> spmv_ms;                     // by iteration; -1: not sampled
+    double gat_sum = 0.0, halo_sum = 0.0;
+    int64_t gat_n = 0, halo_n = 0;
+    PcgTimers(SolveKit *k, int stride, bool init_diag, int64_t maxiter) : kit(k), S(stride > 0 ? stride : 0), skip0(init_diag) {
+        for (int i = 0; i < kTimedSlots; ++i) {
+            tk[i] = -1;
+            tgat[i] = thalo[i] = false;
+        }
+        if (S) spmv_ms.assign((size_t)maxiter, -1.0f);
+    }
+    int sample(hipEvent_t a, hipEvent_t b, float *ms) {
+        PSK_HIP(hipEventSynchronize(b));
+        PSK_HIP(hipEventElapsedTime(ms, a, b));
+        return PSK_OK;
+    }
+    int harvest(int slot) {
+        if (tk[slot] < 0) return PSK_OK;
+        float ms = 0.f;
+        PSK_TRY(sample(kit->ta[slot], kit->tb[slot], &ms));
+        spmv_ms[(size_t)tk[slot]] = ms;
+        tk[slot] = -1;
+        if (tgat[slot]) {
+            PSK_TRY(sample(kit->ga[slot], kit->gb[slot], &ms));
+            gat_sum += ms;
+            ++gat_n;
+            tgat[slot] = false;
+        }
+        if (thalo[slot]) {
+            PSK_TRY(sample(kit->ha[slot], kit->hb[slot], &ms));
+            halo_sum += ms;
+            ++halo_n;
+            thalo[slot] = false;
+        }
+        return PSK_OK;
+    }
+    // iteration k: whether it is timed and its slot, harvested first when the ring has wrapped
+    int begin(int64_t k, int *slot, bool *timed) {
+        *timed = S > 0 && k % S == 0 && !(skip0 && k == 0);
+        *slot = (int)((k / (S > 0 ? S : 1)) % kTimedSlots);
+        if (*timed) {
+            PSK_TRY(harvest(*slot));
+            tk[*slot] = k;
+        }
+        return PSK_OK;
+    }
+    // the means over the harvested slots; nk: iterations whose SpMV ran
+    void finish(int64_t nk, psk_result *res) const {
+        if (!S) return;
+        double tot = 0.0;
+        const int64_t cnt = nk < (int64_t)spmv_ms.size() ? nk : (int64_t)spmv_ms.size();
+        int64_t nt = 0;
+        for (int64_t i = 0; i < cnt; i += S)
+            if (spmv_ms[(size_t)i] >= 0.0f) {
+                tot += spmv_ms[(size_t)i];
+                ++nt;
+            }
+        res->spmv_launches = nt;
+        res->spmv_ms = nt > 0 ? tot / (double)nt : 0.0;
+        res->gather_ms = gat_n > 0 ? gat_sum / (double)gat_n : 0.0;
+        res->halo_ms = halo_n > 0 ? halo_sum / (double)halo_n : 0.0;
+        res->comm_samples = gat_n;
+    }
+};
+
+// the init: the general form, the one fused into the first SpMV (diagonal layout) or pcg_init_kernel; sharded, the
+// ranks' sums gathered and the state set by pcg_init_finish_kernel
+static int pcg_init(PcgRun &r, const StampPoll &poll, const double *b, int32_t loc) {
+    const PcgPlan &pl = r.pl;
+    PcgWork &w = r.w;
+    const int64_t n = pl.n;
+    hipStream_t s = r.s;
+    GridSum gs0;
+    if (!pl.init_diag) PSK_TRY(gridsum_prepare(r.c, pl.gen ? pl.nv : pl.nsl, 2, w.pinit, &gs0));
+    PSK_TRY(gridsum_prepare(r.c, pl.nv, 2, w.part2, &r.gs2));
+    PSK_TRY(gridsum_prepare(r.c, pl.nv, 1, w.part3, &r.gs3));
+    const PcgInitFin fin{r.ctl->tau, w.st, w.udr, poll.hdone(), poll.hgen(), pl.gen ? 1 : 0, 0};
+    r.bd = b;
+    if (!pl.dev_io) {   // host b staged in r (r_0 = b already: K2 of iteration 0 then reads r as usual), or, on
+                        // the general path, in Ap (unused until the first SpMV; its init copies r = b)
+        PSK_TRY(to_device_vec(b, loc, n, pl.gen ? w.Ap : w.r, s));
+        r.bd = pl.gen ? w.Ap : w.r;
+    }
+    const uint64_t seq0 = pl.mbc ? mbox_next(pl.mbc, &gs0) : 0;
+    PSK_HIP(hipEventRecord(r.kit->ev0, s));
+    if (pl.gen) {
+        const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
+        if (n > 0) hipLaunchKernelGGL(pcg_gen_init_kernel, dim3(nb), dim3(kBlock), 0, s, n, r.bd, w.x, w.r);
+        PSK_TRY(prec_apply_dev(r.M, n, w.r, w.u, s));                   // p = precond.applyRight(r)  :98
+        hipLaunchKernelGGL(pcg_gen_init2_kernel, dim3((unsigned)pl.nv), dim3(kBlock), 0, s, n, w.r, w.u, w.p, gs0, fin);
+    } else if (pl.init_diag) {
+        PcgInitFin fin3 = fin;
+        fin3.off = 1;
+        PSK_TRY(launch_pcg_init_diag(r.A, r.bd, pl.jac == 2 ? pl.ds : 1.0, w.p, w.Ap, w.part1, fin3, s));
+    } else {
+        const dim3 gi((unsigned)((pl.nsl + 1) / 2));
+        pcg_dispatch(pl.jac, !pl.sharded, [&](auto J, auto FUSED) {
+            hipLaunchKernelGGL((pcg_init_kernel<decltype(J)::value, decltype(FUSED)::value>), gi, dim3(kBlock), 0, s, n,
+                               r.bd, pl.dinv, pl.ds, w.p, gs0, fin, pl.nsl);
+        });
+    }
+    PSK_HIP(hipGetLastError());
+    if (pl.sharded) {
+        if (pl.mbc) PSK_TRY(mbox_gather(pl.mbc, seq0, 2, w.initg, nullptr, s));
+        else PSK_TRY(allgather(r.A, w.pinit, w.initg, 2, s));
+        hipLaunchKernelGGL(pcg_init_finish_kernel, dim3(1), dim3(64), 0, s, w.initg, pl.P, r.ctl->tau, w.st, w.udr,
+                           poll.hdone(), poll.hgen());
+        PSK_HIP(hipGetLastError());
+    }
+    return PSK_OK;
+}
+
+// K3 of iteration k over tiles [t0, t1)
+static void pcg_k3(PcgRun &r, int64_t k, int64_t t0, int64_t t1) {
+    if (t1 <= t0) return;
+    const PcgPlan &pl = r.pl;
+    PcgWork &w = r.w;
+    const dim3 g3((unsigned)(t1 - t0));
+    const TileMap tm3 = tile_map_for(t1 - t0, false);
+    pcg_dispatch(pl.jac, pl.stag, [&](auto J, auto SG) {
+        hipLaunchKernelGGL((pcg_direction_kernel<decltype(J)::value, decltype(SG)::value && (kPcgStagger > 0)>), g3,
+                           dim3(kBlock), 0, r.s, pl.n, w.x, w.r, w.pr, pl.dinv, pl.ds, w.part1g, w.part2g, pl.P, w.st, w.udr,
+                           w.hist, w.alphas, k, pl.maxiter, r.ctl->fail_on_maxiter, t0, tm3);
+    });
+}
+
+// iteration k: the halo of p_k, K1 (with the flush role), K2, the preconditioner or nothing, K3
+static int pcg_iteration(PcgRun &r, PcgTimers &tm, int64_t k) {
+    const PcgPlan &pl = r.pl;
+    PcgWork &w = r.w;
+    psk_csr *A = r.A;
+    SolveKit *kit = r.kit;
+    hipStream_t s = r.s;
+    const int64_t n = pl.n;
+    // p_k and the buffer K3 writes p_{k+1} into (Jacobi/identity: a ring of kPcgDefer; general: in place)
+    double *pk = pl.gen ? w.p : w.pr.b[k % kPcgDefer];
+    double *pn = pl.gen ? w.p : w.pr.b[(k + 1) % kPcgDefer];
+    int slot;
+    bool timed;
+    PSK_TRY(tm.begin(k, &slot, &timed));
+    if (r.halo_pending) {   // exchanged during the previous K3
+        PSK_HIP(hipStreamWaitEvent(s, kit->ev_b, 0));
+        r.halo_pending = false;
+    } else if (A->comm) {
+        const bool th = timed && !A->comm->dry && !A->peers.empty();
+        if (th) PSK_HIP(hipEventRecord(kit->ha[slot], s));
+        PSK_TRY(halo_exchange(A, pk, s));
+        if (th) {
+            PSK_HIP(hipEventRecord(kit->hb[slot], s));
+            tm.thalo[slot] = true;
+        }
+    }
+    // a timed launch records its events in its own dispatch (kernel start / end)
+    uint64_t seq1 = 0;
+    // staggered: launch k >= 1 also brings block k mod kPcgStagger of x up to date (launch_spmv sizes the role)
+    const SpmvFlush fl{w.x, w.alphas, w.pr, k, pl.nv, 0, 0, 0, 0};
+    if (!(pl.init_diag && k == 0))
+        PSK_TRY(launch_spmv(A, kSpmvDot, pk, w.Ap, nullptr, nullptr, w.part1, &w.st->done, s, timed ? kit->ta[slot] : nullptr,
+                            timed ? kit->tb[slot] : nullptr, 0, pl.mbc ? &seq1 : nullptr, pl.stag && k >= 1 ? &fl : nullptr));
+    // K2/K3 tiles in block order: XCD bands matching the SpMV's, and bands walked in alternating
+    // directions (a serpentine over SpMV, K2, K3 meant to re-read Ap, r and p from the Infinity Cache),
+    // measured no faster (round 4, profiles/r4_spmv_ab.txt: band1 / band2)
+    const TileMap tm2 = tile_map_for(pl.nv, false);
+    if (pl.sharded) {
+        hipEvent_t g0 = timed ? kit->ga[slot] : nullptr, g1 = timed ? kit->gb[slot] : nullptr;
+        if (pl.mbc) {
+            PSK_TRY(mbox_gather(pl.mbc, seq1, 1, w.part1g, &w.st->done, s, g0, g1));
+        } else {
+            if (g0) PSK_HIP(hipEventRecord(g0, s));
+            PSK_TRY(allgather(A, w.part1, w.part1g, 1, s));
+            if (g1) PSK_HIP(hipEventRecord(g1, s));
+        }
+        if (timed) tm.tgat[slot] = true;
+    }
+    GridSum gs2k = r.gs2;   // this iteration's mailbox slot (sharded with a mailbox)
+    const uint64_t seq2 = pl.mbc ? mbox_next(pl.mbc, &gs2k) : 0;
+    // the general path copied r = b in its init (pcg_gen_init_kernel): it never takes the FIRST form
+    const dim3 gk((unsigned)pl.nv);
+    pcg_dispatch(pl.jac, k == 0 && !pl.gen && pl.dev_io, [&](auto J, auto FIRST) {
+        hipLaunchKernelGGL((pcg_update_kernel<decltype(J)::value, decltype(FIRST)::value>), gk, dim3(kBlock), 0, s, n, w.r,
+                           r.bd, w.Ap, pl.dinv, pl.ds, w.part1g, pl.P, gs2k, w.st, w.udr, k, tm2);
+    });
+    if (pl.sharded) {
+        if (pl.mbc) PSK_TRY(mbox_gather(pl.mbc, seq2, 2, w.part2g, &w.st->done, s));
+        else PSK_TRY(allgather(A, w.part2, w.part2g, 2, s));
+    }
+    if (pl.gen) {
+        PSK_TRY(prec_apply_dev(r.M, n, w.r, w.u, s));          // u = M^-1 r  :123
+        hipLaunchKernelGGL(pcg_dot_kernel, gk, dim3(kBlock), 0, s, n, w.u, w.r, r.gs3, w.st);
+        hipLaunchKernelGGL(pcg_gen_direction_kernel, gk, dim3(kBlock), 0, s, n, w.x, w.u, w.p, w.part1, w.part2,
+                           w.part3, w.st, w.udr, w.hist, k, pl.maxiter, r.ctl->fail_on_maxiter);
+    } else if (pl.overlap && k + 1 < pl.maxiter) {
+        // the tiles holding the rows the neighbours need first, then their halo exchange on the
+        // second stream while the other tiles run; the next SpMV waits for it
+        pcg_k3(r, k, 0, pl.ov_lo);
+        pcg_k3(r, k, pl.ov_hi, pl.nv);
+        PSK_TRY(halo_exchange_async(A, pn, s, r.cs, kit->ev_a, kit->ev_b, timed ? kit->ha[slot] : nullptr,
+                                    timed ? kit->hb[slot] : nullptr));
+        if (timed) tm.thalo[slot] = true;
+        pcg_k3(r, k, pl.ov_lo, pl.ov_hi);
+        r.halo_pending = true;
+    } else {
+        pcg_k3(r, k, 0, pl.nv);
+    }
+    PSK_HIP(hipGetLastError());
+    return PSK_OK;
+}
+
+// the end of the loop: one launch and one synchronisation for the state, the ticket-counter scan and the gridsum
+// error word, all written by pcg_finish_kernel into the host-mapped words (round 5: was two copies and a kernel)
+static int pcg_finish(PcgRun &r, PcgTimers &tm, PcgState *hs, psk_result *res) {
+    SolveKit *kit = r.kit;
+    // a halo exchange still in flight (the host stopped enqueueing first) completes before the end
+    if (r.halo_pending) PSK_HIP(hipStreamWaitEvent(r.s, kit->ev_b, 0));
+    r.halo_pending = false;
+    PSK_HIP(hipEventRecord(kit->ev1, r.s));
+    int64_t *hw = kit->hmap + kPcgFinishWord;
+    hipLaunchKernelGGL(pcg_finish_kernel, dim3(1), dim3(kBlock), 0, r.s, r.w.st, r.c->gs_cnt, r.c->gs_err, hw);
+    PSK_HIP(hipGetLastError());
+    PSK_HIP(hipStreamSynchronize(r.s));
+    std::memcpy(hs, hw, sizeof(PcgState));
+    PSK_TRY(gridsum_check_result(r.c, (int32_t)hw[kPcgStateWords]));
+    if (r.pl.gen) PSK_TRY(prec_check_error(r.M, r.s));
+    for (int i = 0; i < kTimedSlots; ++i) PSK_TRY(tm.harvest(i));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, kit->ev0, kit->ev1);
+    res->loop_ms = ms;
+    return PSK_OK;
+}
+
+// The state hs of a finished loop that enqueued `launched` iterations, decoded into res; the history, and x with
+// whatever the end of the solve left pending. *nk: iterations whose SpMV ran (the timing count).
+static int pcg_report(const PcgState &hs, const PcgPlan &pl, int64_t launched, const psk_ctl *ctl, const PcgWork &w,
+                      hipStream_t s, psk_result *res, double *hist, double *xout, int32_t loc, int64_t *nk) {
+    const int64_t n = pl.n, maxiter = pl.maxiter;
+    res->norm_b = hs.normB;
+    // nhist: iterations that reported a residual (K3 wrote hist[k]) — a dot(p,Ap) breakdown at k ran the SpMV
+    // of k but reports only 0..k-1, as the reference's loop does (PCGSolver.py:114-115 returns before :126)
+    int64_t nhist = 0;
+    if (hs.done == 1) {
+        res->status = PSK_CONVERGED;
+        res->success = 1;
+        res->iters = hs.iters;
+        res->resid = hs.resid;
+        res->exit = hs.normB == 0.0 ? PSK_EXIT_NONE : hs.resid <= hs.tauNormB ? PSK_EXIT_TOLERANCE : PSK_EXIT_MAXITER;
+        *nk = nhist = hs.normB == 0.0 ? 0 : hs.iters;
+    } else if (hs.done == 2) {
+        res->status = PSK_BREAKDOWN;
+        res->exit = PSK_EXIT_DOT_BREAKDOWN;
+        res->success = 0;
+        res->iters = hs.iters;
+        res->resid = NAN;
+        set_msg(res, hs.brk_kind == 1 ? "breakdown dot(u,r)==0" : "breakdown dot(p, Ap)==0");
+        *nk = hs.brk_kind == 1 ? 0 : hs.iters + 1;
+        nhist = hs.brk_kind == 1 ? 0 : hs.iters;
+    } else {
+        // handleMaxiter(k=maxiter-1, ...) (IterativeSolver.py:115-129); maxiter==0 -> k unset
+        res->status = PSK_MAXITER;
+        res->exit = PSK_EXIT_MAXITER;
+        res->success = 0;
+        res->iters = maxiter > 0 ? maxiter - 1 : 0;
+        set_msg(res, "failure to converge");
+        *nk = nhist = launched;
+    }
+    // residual history (only when asked for), the recursive residual and the solution
+    const int64_t nh = nhist < maxiter ? nhist : maxiter;
+    if (hist && nh > 0) PSK_HIP(hipMemcpy(hist, w.hist, (size_t)nh * 8, hipMemcpyDeviceToHost));
+    res->hist_len = nh;
+    res->resid_recursive = nh > 0 ? hs.last_hist : hs.normB;
+    if (res->status == PSK_MAXITER) res->resid = maxiter > 0 ? res->resid_recursive : hs.normB;
+    bool x_written = hs.x_written != 0;
+    bool more = !pl.dev_io;   // work enqueued after the sync: the caller's x is ready only after another sync
+    // a dot(p,Ap) breakdown at k: the iterations since the last flush deferred their x updates (staggered: every
+    // SpMV launch 1 .. k ran its flush role, so the schedule says per block what is stored and what is pending;
+    // uniform: one block)
+    if (!pl.gen && hs.done == 2 && hs.brk_kind != 1 && n > 0) {
+        bool pending = false;
+        const int nblk = pl.stag ? kPcgStagger : 1;
+        for (int b = 0; b < nblk; ++b) {
+            if (pl.stag && (int64_t)b * pcg_block_tiles(pl.nv, kPcgStagger) >= pl.nv) continue;   // owns no tile
+            const PcgPend pd = pl.stag ? pcg_flush_pending(kPcgStagger, b, hs.iters, false) : pcg_uniform_pending(hs.iters);
+            pending = pending || pd.first <= pd.last;
+            x_written = x_written || pd.first > 0;
+        }
+        if (pending) {
+            PSK_TRY(launch_pcg_flush(n, w.x, w.pr, w.alphas, (int64_t)hs.iters, pl.stag, s));
+            x_written = true;   // rows with nothing pending were stored by an earlier flush
+            more = true;        // also when an earlier flush had already stored x
+        }
+    }
+    // no iteration stored x (b = 0, dot(u,r) = 0 at the start, maxiter = 0, or a dot(p,Ap) breakdown at k = 0):
+    // the solution is x0 = 0
+    if (!x_written && n > 0) {
+        PSK_HIP(hipMemsetAsync(w.x, 0, (size_t)n * 8, s));
+        more = true;
+    }
+    if (!pl.dev_io) PSK_TRY(from_device_vec(w.x, loc, n, xout, s));
+    if (more) PSK_HIP(hipStreamSynchronize(s));
+    return PSK_OK;
+}
+
+// the phases in order; the caller drains the stream when one fails
+static int pcg_solve(PcgRun &r, const double *b, double *xout, psk_result *res, double *hist, int32_t loc) {
+    const PcgPlan &pl = r.pl;
+    PSK_TRY(pcg_workspace(r.A, pl.maxiter, pl.gen, !pl.dev_io, pl.P, r.w));
+    if (pl.dev_io) r.w.x = xout;
+    PSK_TRY(solve_kit(r.c, r.ctl->time_kernels > 0, &r.kit));
+    if (pl.overlap) PSK_TRY(comm_stream(r.c, &r.cs));
+    StampPoll poll(r.kit);   // the host-mapped done stamp the kernels write (set_done)
+    PcgTimers tm(r.kit, r.ctl->time_kernels, pl.init_diag, pl.maxiter);
+    PSK_TRY(pcg_init(r, poll, b, loc));
+    int64_t launched = 0, nk = 0;
+    for (int64_t k = 0; k < pl.maxiter; ++k) {
+        bool stop;
+        PSK_TRY(poll.step<2>(k, pl.C, r.s, &stop));
+        if (stop) break;
+        PSK_TRY(pcg_iteration(r, tm, k));
+        launched = k + 1;
+    }
+    PcgState hs;
+    PSK_TRY(pcg_finish(r, tm, &hs, res));
+    PSK_TRY(pcg_report(hs, pl, launched, r.ctl, r.w, r.s, res, hist, xout, loc, &nk));
+    tm.finish(nk, res);
+    return PSK_OK;
 }
 
 }  // namespace psk
@@ -477,377 +890,20 @@ extern "C" int psk_pcg(const psk_csr *Ac, const psk_prec *M, const double *b, do
     if (ctl->maxiter < 0) return fail(PSK_ERR_ARG, "psk_pcg: maxiter < 0");
     if (M && M->n != Ac->n) return fail(PSK_ERR_ARG, "psk_pcg: preconditioner size mismatch");
     if (!Ac->comm && Ac->ncols != Ac->n) return fail(PSK_ERR_ARG, "psk_pcg: matrix must be square");
-    psk_csr *A = const_cast<psk_csr *>(Ac);
-    Context *c;
-    PSK_TRY(ctx(&c));
-    std::lock_guard<std::mutex> solve_lock(c->solve_mu);
-    hipStream_t s = c->stream;
+    PcgRun r{};
+    r.A = const_cast<psk_csr *>(Ac);
+    r.M = M;
+    r.ctl = ctl;
+    PSK_TRY(ctx(&r.c));
+    std::lock_guard<std::mutex> solve_lock(r.c->solve_mu);
+    r.s = r.c->stream;
     std::memset(res, 0, sizeof(*res));
-    const int64_t n = A->n, maxiter = ctl->maxiter;
-    // general preconditioner (ILU): u = M^-1 r materialised between K2 and K3
-    const bool gen = prec_is_general(M);
-    if (gen && A->comm) return fail(PSK_ERR_UNSUPPORTED, "psk_pcg: ILU preconditioning of a sharded matrix");
-    // sharded: P ranks, scalars gathered (not all-reduced) and summed in rank order on every rank
-    const bool sharded = A->comm != nullptr;
-    const int P = sharded ? A->comm->nranks : 1;
-    const bool dev_io = loc == PSK_DEVICE;
-    PcgWork w;
-    PSK_TRY(pcg_workspace(A, maxiter, gen, !dev_io, P, w));
-    if (dev_io) w.x = xout;   // b and x in HBM: read b in place, write x in place
-    SolveKit *kit;
-    PSK_TRY(solve_kit(c, ctl->time_kernels > 0, &kit));
-    const double *dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
-    const int jac = !dinv ? 0 : M->dinv_uniform ? 2 : 1;
-    const double ds = jac == 2 ? M->dinv_value : 0.0;
-    // one-shot grid of K0/K2/K3 (one 512-element tile per workgroup); K0/K1/K2 finish their dot products
-    // in-launch (gridsum), so the loop's scalars are part1[0] = p.Ap and part2[0..1] = (r.r, u.r)
-    const int64_t nv = n > 0 ? (n + kVecTile - 1) / kVecTile : 1;
-    if (nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_pcg: vector too long for a one-shot grid");
-    // the init: unsharded with the diagonal layout (5 diagonals, one DInv value or none) fused into the first
-    // SpMV (spmv_diag.hip pcg_init_diag_kernel, [p.Ap, b.b, u.r] into part1); otherwise pcg_init_kernel over the
-    // SpMV's 256-row tiles (the same bits for b.b and u.r), or the general path's init over 512-element tiles
-    const bool init_diag = !gen && !sharded && (jac == 0 || jac == 2) && pcg_init_diag_eligible(A);
-    // the staggered x flush (pcg_state.hpp): unsharded Jacobi/identity solves whose in-loop SpMV is the pair-row
-    // diagonal kernel; every other path keeps the uniform flush in K3
-    const bool stag = pcg_staggers(A, M);
-    const int64_t nsl = n > 0 ? (n + kBlock - 1) / kBlock : 1;
-    GridSum gs0, gs2, gs3;
-    if (!init_diag) PSK_TRY(gridsum_prepare(c, gen ? nv : nsl, 2, w.pinit, &gs0));
-    PSK_TRY(gridsum_prepare(c, nv, 2, w.part2, &gs2));
-    PSK_TRY(gridsum_prepare(c, nv, 1, w.part3, &gs3));
-    // the host-mapped done stamp the kernels write (set_done); no kernel of an earlier solve is running
-    volatile int64_t *hdone = kit->hmap;
-    const int64_t hgen = (int64_t)(++kit->solve_gen & 0x7FFFFF) << kStampGenShift;
-    *hdone = 0;
-    const PcgInitFin fin{ctl->tau, w.st, w.udr, const_cast<int64_t *>(hdone), hgen, gen ? 1 : 0, 0};
-    const double *bd = b;
-    if (!dev_io) {   // host b staged in r (r_0 = b already: K2 of iteration 0 then reads r as usual), or, on
-                     // the general path, in Ap (unused until the first SpMV; its init copies r = b)
-        PSK_TRY(to_device_vec(b, loc, n, gen ? w.Ap : w.r, s));
-        bd = gen ? w.Ap : w.r;
-    }
-    // sharded with a mailbox (psk_comm_mailbox): the ranks' scalars go kernel -> mailbox -> gather kernel
-    // instead of ncclAllGather; same gathered arrays, same rank-order sums
-    psk_comm *mbc = sharded && A->comm->mb ? A->comm : nullptr;
-    uint64_t seq0 = 0;
-    if (mbc) seq0 = mbox_next(mbc, &gs0);
-    PSK_HIP(hipEventRecord(kit->ev0, s));
-    const dim3 gk((unsigned)nv);
-    if (gen) {
-        const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
-        if (n > 0) hipLaunchKernelGGL(pcg_gen_init_kernel, dim3(nb), dim3(kBlock), 0, s, n, bd, w.x, w.r);
-        PSK_TRY(prec_apply_dev(M, n, w.r, w.u, s));                   // p = precond.applyRight(r)  :98
-        hipLaunchKernelGGL(pcg_gen_init2_kernel, gk, dim3(kBlock), 0, s, n, w.r, w.u, w.p, gs0, fin);
-    } else if (init_diag) {
-        PcgInitFin fin3 = fin;
-        fin3.off = 1;
-        PSK_TRY(launch_pcg_init_diag(A, bd, jac == 2 ? ds : 1.0, w.p, w.Ap, w.part1, fin3, s));
-    } else {
-        const dim3 gi((unsigned)((nsl + 1) / 2));
-#define PSK_PCG_INIT(J, F) \
-        hipLaunchKernelGGL((pcg_init_kernel<J, F>), gi, dim3(kBlock), 0, s, n, bd, dinv, ds, w.p, gs0, fin, nsl)
-        if (jac == 2) { if (sharded) PSK_PCG_INIT(2, false); else PSK_PCG_INIT(2, true); }
-        else if (jac == 1) { if (sharded) PSK_PCG_INIT(1, false); else PSK_PCG_INIT(1, true); }
-        else { if (sharded) PSK_PCG_INIT(0, false); else PSK_PCG_INIT(0, true); }
-#undef PSK_PCG_INIT
-    }
-    PSK_HIP(hipGetLastError());
-    if (sharded) {
-        if (mbc) PSK_TRY(mbox_gather(mbc, seq0, 2, w.initg, nullptr, s));
-        else PSK_TRY(allgather(A, w.pinit, w.initg, 2, s));
-        hipLaunchKernelGGL(pcg_init_finish_kernel, dim3(1), dim3(64), 0, s, w.initg, P, ctl->tau, w.st, w.udr,
-                           const_cast<int64_t *>(hdone), hgen);
-        PSK_HIP(hipGetLastError());
-    }
-
-    // polling: every C iterations an event; the host waits on the event L chunks back and then reads the
-    // host-mapped done word the kernels set (set_done)
-    const int L = 2, NS = kPollSlots;
-    static_assert(kPollSlots >= L + 2, "poll slots");
-    int C = ctl->check_every > 0 ? ctl->check_every : (n >= (1 << 20) ? 2 : 16);
-    hipEvent_t *fev = kit->fev;
-    // optional SpMV timing ring
-    const int TP = kTimedSlots;
-    hipEvent_t *ta = kit->ta, *tb = kit->tb;
-    int64_t tk[kTimedSlots];
-    bool tgat[kTimedSlots], thalo[kTimedSlots];   // sharded: the slot's gather / halo events were recorded
-    for (int i = 0; i < TP; ++i) {
-        tk[i] = -1;
-        tgat[i] = thalo[i] = false;
-    }
-    std::vector<float> spmv_ms;
-    if (ctl->time_kernels) spmv_ms.assign((size_t)maxiter, -1.0f);   // -1: not sampled
-    double gat_sum = 0.0, halo_sum = 0.0;
-    int64_t gat_n = 0, halo_n = 0;
-    auto harvest = [&](int slot) -> int {
-        if (tk[slot] < 0) return PSK_OK;
-        float ms = 0.f;
-        PSK_HIP(hipEventSynchronize(tb[slot]));
-        PSK_HIP(hipEventElapsedTime(&ms, ta[slot], tb[slot]));
-        spmv_ms[(size_t)tk[slot]] = ms;
-        tk[slot] = -1;
-        if (tgat[slot]) {
-            PSK_HIP(hipEventSynchronize(kit->gb[slot]));
-            PSK_HIP(hipEventElapsedTime(&ms, kit->ga[slot], kit->gb[slot]));
-            gat_sum += ms;
-            ++gat_n;
-            tgat[slot] = false;
-        }
-        if (thalo[slot]) {
-            PSK_HIP(hipEventSynchronize(kit->hb[slot]));
-            PSK_HIP(hipEventElapsedTime(&ms, kit->ha[slot], kit->hb[slot]));
-            halo_sum += ms;
-            ++halo_n;
-            thalo[slot] = false;
-        }
-        return PSK_OK;
-    };
-
-    // halo overlap (sharded, Jacobi/identity): when every row a neighbour needs lies in the first ov_lo
-    // or the last nv - ov_hi K3 tiles (row-block shards of a banded matrix: one grid line each side),
-    // those tiles run first and the exchange of p overlaps the remaining tiles of K3
-    int64_t ov_lo = 0, ov_hi = nv;
-    // On by default (PSK_HALO_OVERLAP=0 turns it off); DESIGN.md §6 states the rule: the overlap moves
-    // no arithmetic (sharded histories are bit-identical either way) and takes the halo's latency off
-    // the critical path whenever K3's interior tiles outlast the exchange, which they do at every
-    // size the 8-GPU run uses (>= 1.25M rows per rank); an 8-GPU A/B of the driver's run decides it.
-    static const bool overlap_on = [] {
-        const char *e = std::getenv("PSK_HALO_OVERLAP");
-        return !(e && std::atoi(e) == 0);
-    }();
-    const bool overlap = overlap_on && sharded && !gen && halo_split(A, kVecTile, nv, ov_lo, ov_hi);
-    hipStream_t cs = nullptr;
-    hipEvent_t ev_k3a = kit->ev_a, ev_halo = kit->ev_b;
-    bool halo_pending = false;
-    if (overlap) PSK_TRY(comm_stream(c, &cs));
-
-    int64_t launched = 0;
-    int rc = PSK_OK;
-    for (int64_t k = 0; k < maxiter && rc == PSK_OK; ++k) {
-        if (k > 0 && k % C == 0) {
-            const int64_t chunk = k / C;   // chunks fully launched
-            const int slot = (int)((chunk - 1) % NS);
-            if (hipEventRecord(fev[slot], s) != hipSuccess) rc = fail(PSK_ERR_HIP, "event");
-            if (rc == PSK_OK && chunk - 1 - L >= 0) {
-                const int os = (int)((chunk - 1 - L) % NS);
-                if (hipEventSynchronize(fev[os]) != hipSuccess) rc = fail(PSK_ERR_HIP, "event sync");
-                else {
-                    const int64_t hv = *hdone;   // a stamp of this solve only (its generation)
-                    if ((hv & ~kStampMask) == hgen && (hv & kStampMask) != 0 &&
-                        (hv & kStampMask) <= (chunk - L) * (int64_t)C + 1)
-                        break;
-                }
-            }
-            if (rc != PSK_OK) break;
-        }
-        // p_k and the buffer K3 writes p_{k+1} into (Jacobi/identity: a ring of kPcgDefer; general: in place)
-        double *pk = gen ? w.p : w.pr.b[k % kPcgDefer];
-        double *pn = gen ? w.p : w.pr.b[(k + 1) % kPcgDefer];
-        // every time_kernels-th SpMV between two events (sampled: an event pair costs ~5% of an
-        // iteration at N = 10M); sharded, the same iterations time this rank's p.Ap gather and the halo
-        // exchange of the iteration (ABI 4: psk_result.gather_ms / halo_ms)
-        // (init_diag: iteration 0's SpMV ran inside the init launch, not sampled)
-        const bool timed = ctl->time_kernels > 0 && k % ctl->time_kernels == 0 && !(init_diag && k == 0);
-        int slot = (int)((k / (ctl->time_kernels > 0 ? ctl->time_kernels : 1)) % TP);
-        if (timed) {
-            if ((rc = harvest(slot)) != PSK_OK) break;
-            tk[slot] = k;
-        }
-        if (halo_pending) {   // exchanged during the previous K3
-            if (hipStreamWaitEvent(s, ev_halo, 0) != hipSuccess) { rc = fail(PSK_ERR_HIP, "halo wait"); break; }
-            halo_pending = false;
-        } else if (A->comm) {
-            const bool th = timed && !A->comm->dry && !A->peers.empty();
-            if (th && hipEventRecord(kit->ha[slot], s) != hipSuccess) { rc = fail(PSK_ERR_HIP, "event"); break; }
-            if ((rc = halo_exchange(A, pk, s)) != PSK_OK) break;
-            if (th) {
-                if (hipEventRecord(kit->hb[slot], s) != hipSuccess) { rc = fail(PSK_ERR_HIP, "event"); break; }
-                thalo[slot] = true;
-            }
-        }
-        // a timed launch records its events in its own dispatch (kernel start / end)
-        uint64_t seq1 = 0;
-        // staggered: launch k >= 1 also brings block k mod kPcgStagger of x up to date (launch_spmv sizes the role)
-        SpmvFlush fl{w.x, w.alphas, w.pr, k, nv, 0, 0, 0, 0};
-        if (!(init_diag && k == 0) &&
-            (rc = launch_spmv(A, kSpmvDot, pk, w.Ap, nullptr, nullptr, w.part1, &w.st->done, s, timed ? ta[slot] : nullptr,
-                              timed ? tb[slot] : nullptr, 0, mbc ? &seq1 : nullptr, stag && k >= 1 ? &fl : nullptr)) !=
-                PSK_OK)
-            break;
-        // K2/K3 tiles in block order: XCD bands matching the SpMV's, and bands walked in alternating
-        // directions (a serpentine over SpMV, K2, K3 meant to re-read Ap, r and p from the Infinity Cache),
-        // measured no faster (round 4, profiles/r4_spmv_ab.txt: band1 / band2)
-        const TileMap tm2 = tile_map_for(nv, false);
-        if (sharded) {
-            hipEvent_t g0 = timed ? kit->ga[slot] : nullptr, g1 = timed ? kit->gb[slot] : nullptr;
-            if (mbc) {
-                rc = mbox_gather(mbc, seq1, 1, w.part1g, &w.st->done, s, g0, g1);
-            } else {
-                if (g0 && hipEventRecord(g0, s) != hipSuccess) rc = fail(PSK_ERR_HIP, "event");
-                if (rc == PSK_OK) rc = allgather(A, w.part1, w.part1g, 1, s);
-                if (rc == PSK_OK && g1 && hipEventRecord(g1, s) != hipSuccess) rc = fail(PSK_ERR_HIP, "event");
-            }
-            if (rc != PSK_OK) break;
-            if (timed) tgat[slot] = true;
-        }
-        GridSum gs2k = gs2;   // this iteration's mailbox slot (sharded with a mailbox)
-        const uint64_t seq2 = mbc ? mbox_next(mbc, &gs2k) : 0;
-        // the general path copied r = b in its init (pcg_gen_init_kernel): it never takes the FIRST form
-        const bool first = k == 0 && !gen && dev_io;
-        const double *pap_k = w.part1g;
-#define PSK_PCG_K2(J, F)                                                                                       \
-        hipLaunchKernelGGL((pcg_update_kernel<J, F>), gk, dim3(kBlock), 0, s, n, w.r, bd, w.Ap, dinv, ds, pap_k,     \
-                           P, gs2k, w.st, w.udr, k, tm2)
-        if (jac == 2) { if (first) PSK_PCG_K2(2, true); else PSK_PCG_K2(2, false); }
-        else if (jac == 1) { if (first) PSK_PCG_K2(1, true); else PSK_PCG_K2(1, false); }
-        else { if (first) PSK_PCG_K2(0, true); else PSK_PCG_K2(0, false); }
-#undef PSK_PCG_K2
-        if (sharded && (rc = mbc ? mbox_gather(mbc, seq2, 2, w.part2g, &w.st->done, s)
-                                 : allgather(A, w.part2, w.part2g, 2, s)) != PSK_OK)
-            break;
-        if (gen) {
-            if ((rc = prec_apply_dev(M, n, w.r, w.u, s)) != PSK_OK) break;          // u = M^-1 r  :123
-            hipLaunchKernelGGL(pcg_dot_kernel, gk, dim3(kBlock), 0, s, n, w.u, w.r, gs3, w.st);
-            hipLaunchKernelGGL(pcg_gen_direction_kernel, gk, dim3(kBlock), 0, s, n, w.x, w.u, w.p, w.part1, w.part2,
-                               w.part3, w.st, w.udr, w.hist, k, maxiter, ctl->fail_on_maxiter);
-        } else {
-            auto k3 = [&](int64_t t0, int64_t t1) {   // K3 over tiles [t0, t1)
-                if (t1 <= t0) return;
-                const dim3 g3((unsigned)(t1 - t0));
-                const TileMap tm3 = tile_map_for(t1 - t0, false);
-#define PSK_PCG_K3(J, SG)                                                                                      \
-                hipLaunchKernelGGL((pcg_direction_kernel<J, SG>), g3, dim3(kBlock), 0, s, n, w.x, w.r, w.pr, dinv, ds, \
-                                   w.part1g, w.part2g, P, w.st, w.udr, w.hist, w.alphas, k, maxiter,               \
-                                   ctl->fail_on_maxiter, t0, tm3)
-                if (jac == 2) { if (stag) PSK_PCG_K3(2, (kPcgStagger > 0)); else PSK_PCG_K3(2, false); }
-                else if (jac == 1) { if (stag) PSK_PCG_K3(1, (kPcgStagger > 0)); else PSK_PCG_K3(1, false); }
-                else { if (stag) PSK_PCG_K3(0, (kPcgStagger > 0)); else PSK_PCG_K3(0, false); }
-#undef PSK_PCG_K3
-            };
-            if (overlap && k + 1 < maxiter) {
-                // the tiles holding the rows the neighbours need first, then their halo exchange on the
-                // second stream while the other tiles run; the next SpMV waits for it
-                k3(0, ov_lo);
-                k3(ov_hi, nv);
-                if ((rc = halo_exchange_async(A, pn, s, cs, ev_k3a, ev_halo, timed ? kit->ha[slot] : nullptr,
-                                              timed ? kit->hb[slot] : nullptr)) != PSK_OK)
-                    break;
-                if (timed) thalo[slot] = true;
-                k3(ov_lo, ov_hi);
-                halo_pending = true;
-            } else {
-                k3(0, nv);
-            }
-        }
-        if (hipGetLastError() != hipSuccess) { rc = fail(PSK_ERR_HIP, "pcg launch"); break; }
-        launched = k + 1;
-    }
-    // a halo exchange still in flight (the host stopped enqueueing first) completes before the end
-    if (halo_pending && hipStreamWaitEvent(s, ev_halo, 0) != hipSuccess && rc == PSK_OK) rc = fail(PSK_ERR_HIP, "halo wait");
-    if (rc == PSK_OK && hipEventRecord(kit->ev1, s) != hipSuccess) rc = fail(PSK_ERR_HIP, "event");
-    // one launch and one synchronisation for the state, the ticket-counter scan and the gridsum error word,
-    // all written by pcg_finish_kernel into the host-mapped words (round 5: was two copies and a kernel)
-    int64_t *hw = kit->hmap + kPcgFinishWord;
-    if (rc == PSK_OK) {
-        hipLaunchKernelGGL(pcg_finish_kernel, dim3(1), dim3(kBlock), 0, s, w.st, c->gs_cnt, c->gs_err, hw);
-        if (hipGetLastError() != hipSuccess) rc = fail(PSK_ERR_HIP, "pcg finish");
-    }
-    if (rc == PSK_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(PSK_ERR_HIP, "pcg sync");
-    PcgState hs;
-    std::memcpy(&hs, hw, sizeof(PcgState));
-    if (rc == PSK_OK) rc = gridsum_check_result(c, (int32_t)hw[kPcgStateWords]);
-    if (rc == PSK_OK && gen) rc = prec_check_error(M, s);
-    if (rc == PSK_OK && ctl->time_kernels)
-        for (int i = 0; i < TP && rc == PSK_OK; ++i) rc = harvest(i);
-    if (rc == PSK_OK) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, kit->ev0, kit->ev1);
-        res->loop_ms = ms;
-        res->norm_b = hs.normB;
-        // nk: iterations whose SpMV ran (the timing count); nhist: iterations that reported a
-        // residual (K3 wrote hist[k]) — a dot(p,Ap) breakdown at k ran the SpMV of k but reports
-        // only 0..k-1, as the reference's loop does (PCGSolver.py:114-115 returns before :126)
-        int64_t nk = 0, nhist = 0;
-        if (hs.done == 1) {
-            res->status = PSK_CONVERGED;
-            res->success = 1;
-            res->iters = hs.iters;
-            res->resid = hs.resid;
-            res->exit = hs.normB == 0.0 ? PSK_EXIT_NONE
-                        : hs.resid <= hs.tauNormB ? PSK_EXIT_TOLERANCE : PSK_EXIT_MAXITER;
-            nk = nhist = hs.normB == 0.0 ? 0 : hs.iters;
-        } else if (hs.done == 2) {
-            res->status = PSK_BREAKDOWN;
-            res->exit = PSK_EXIT_DOT_BREAKDOWN;
-            res->success = 0;
-            res->iters = hs.iters;
-            res->resid = NAN;
-            set_msg(res, hs.brk_kind == 1 ? "breakdown dot(u,r)==0" : "breakdown dot(p, Ap)==0");
-            nk = hs.brk_kind == 1 ? 0 : hs.iters + 1;
-            nhist = hs.brk_kind == 1 ? 0 : hs.iters;
-        } else {
-            // handleMaxiter(k=maxiter-1, ...) (IterativeSolver.py:115-129); maxiter==0 -> k unset
-            res->status = PSK_MAXITER;
-            res->exit = PSK_EXIT_MAXITER;
-            res->success = 0;
-            res->iters = maxiter > 0 ? maxiter - 1 : 0;
-            set_msg(res, "failure to converge");
-            nk = nhist = launched;
-        }
-        // residual history (only when asked for), the recursive residual and the solution
-        const int64_t nh = nhist < maxiter ? nhist : maxiter;
-        if (hist && nh > 0 && hipMemcpy(hist, w.hist, (size_t)nh * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(PSK_ERR_HIP, "hist copy");
-        if (rc == PSK_OK) {
-            res->hist_len = nh;
-            res->resid_recursive = nh > 0 ? hs.last_hist : hs.normB;
-            if (res->status == PSK_MAXITER) res->resid = maxiter > 0 ? res->resid_recursive : hs.normB;
-            bool x_written = hs.x_written != 0;
-            // a dot(p,Ap) breakdown at k: the iterations since the last flush deferred their x updates
-            bool more = !dev_io;   // work enqueued after the sync: the caller's x is ready only after another sync
-            // (staggered: every SpMV launch 1 .. k ran its flush role, so the schedule says per block what is
-            // stored and what is pending; uniform: one block)
-            if (!gen && hs.done == 2 && hs.brk_kind != 1 && n > 0) {
-                bool pending = false;
-                const int nblk = stag ? kPcgStagger : 1;
-                for (int b = 0; b < nblk; ++b) {
-                    if (stag && (int64_t)b * pcg_block_tiles(nv, kPcgStagger) >= nv) continue;   // owns no tile
-                    const PcgPend pd = stag ? pcg_flush_pending(kPcgStagger, b, hs.iters, false) : pcg_uniform_pending(hs.iters);
-                    pending = pending || pd.first <= pd.last;
-                    x_written = x_written || pd.first > 0;
-                }
-                if (pending) {
-                    rc = launch_pcg_flush(n, w.x, w.pr, w.alphas, (int64_t)hs.iters, stag, s);
-                    x_written = true;   // rows with nothing pending were stored by an earlier flush
-                    more = true;   // also when an earlier flush had already stored x
-                }
-            }
-            // no iteration stored x (b = 0, dot(u,r) = 0 at the start, maxiter = 0, or a dot(p,Ap)
-            // breakdown at k = 0): the solution is x0 = 0
-            if (rc == PSK_OK && !x_written && n > 0) {
-                if (hipMemsetAsync(w.x, 0, (size_t)n * 8, s) != hipSuccess) rc = fail(PSK_ERR_HIP, "x zero");
-                more = true;
-            }
-            if (rc == PSK_OK && !dev_io) rc = from_device_vec(w.x, loc, n, xout, s);
-            if (rc == PSK_OK && more && hipStreamSynchronize(s) != hipSuccess) rc = fail(PSK_ERR_HIP, "x copy");
-        }
-        if (ctl->time_kernels) {
-            double tot = 0.0;
-            const int64_t cnt = nk < (int64_t)spmv_ms.size() ? nk : (int64_t)spmv_ms.size();
-            int64_t nt = 0;
-            for (int64_t i = 0; i < cnt; i += ctl->time_kernels)
-                if (spmv_ms[(size_t)i] >= 0.0f) {
-                    tot += spmv_ms[(size_t)i];
-                    ++nt;
-                }
-            res->spmv_launches = nt;
-            res->spmv_ms = nt > 0 ? tot / (double)nt : 0.0;
-            res->gather_ms = gat_n > 0 ? gat_sum / (double)gat_n : 0.0;
-            res->halo_ms = halo_n > 0 ? halo_sum / (double)halo_n : 0.0;
-            res->comm_samples = gat_n;
-        }
-    }
+    PSK_TRY(pcg_plan(Ac, M, ctl, loc, r.pl));
+    const int rc = pcg_solve(r, b, xout, res, hist, loc);
     // a solve that failed on the host side leaves no kernel of its own running behind the next solve
-    if (rc != PSK_OK) (void)hipStreamSynchronize(s);
+    if (rc != PSK_OK) {
+        if (r.halo_pending) (void)hipStreamWaitEvent(r.s, r.kit->ev_b, 0);
+        (void)hipStreamSynchronize(r.s);
+    }
     return rc;
 }

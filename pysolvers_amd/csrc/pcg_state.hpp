@@ -3,6 +3,7 @@
 // flush role of the in-loop SpMV).
 #pragma once
 #include "psk_internal.hpp"
+#include "solve_loop.hpp"
 
 namespace psk {
 
@@ -21,17 +22,8 @@ struct PcgState {
     int32_t pad;
 };
 
-// done = v != 0, and the host-mapped stamp the solve loop polls: k + 2 for a kernel of iteration k, 1
-// for the init (0 = running) — a system-scope store drained before the kernel ends, so once an event
-// recorded after this kernel has completed the host reads the word directly, with no per-chunk
-// device-to-host copy (a blit kernel) on the solver's stream. The stamp lets the host act on the state
-// as of the chunk it waited for, not a later one its GPU has already run: every rank of a sharded
-// solve then stops after the same chunk and enqueues the same collectives.
-// The word is shared by every solve on the device; each solve tags its stamps with its own generation
-// (high bits), so a kernel still queued from an earlier solve that failed on the host side cannot leave a
-// stamp the next solve's poll would act on.
-constexpr int kStampGenShift = 40;
-constexpr int64_t kStampMask = ((int64_t)1 << kStampGenShift) - 1;
+// done = v != 0, and the host-mapped stamp the solve loop polls (solve_loop.hpp, StampPoll): k + 2 for a kernel of
+// iteration k, 1 for the init
 __device__ __forceinline__ void set_done(PcgState *st, int32_t v, int64_t stamp) {
     st->done = v;
     if (st->hdone) {

@@ -10,8 +10,8 @@
 // maxiter), the history entry and the host-mapped done word.
 //
 // The host never drains the queue: it enqueues cycle after cycle, records an event every `check_every` cycles
-// and reads the done word behind an event kLag chunks back (psk_pcg's scheme). By default (check_every 1,
-// kLag 1) at most one cycle past the converging one is enqueued; cycles that run after it find conv_iter >= 0
+// and reads the done word behind an event kVcLag chunks back (solve_loop.hpp StampPoll). By default (check_every 1,
+// kVcLag 1) at most one cycle past the converging one is enqueued; cycles that run after it find conv_iter >= 0
 // and change neither the output, the history nor the state, so the results do not depend on the lag.
 #include "pcg_state.hpp"
 
@@ -39,7 +39,6 @@ static_assert(sizeof(VcState) == 64, "VcState");
 constexpr int kVcGroups = 64, kVcTickStride = 64;
 constexpr size_t kVcTickBytes = (size_t)(kVcGroups + 1) * kVcTickStride * sizeof(uint32_t);
 constexpr int kVcLag = 1;
-static_assert(kPollSlots >= kVcLag + 2, "poll slots");
 
 __device__ __forceinline__ int64_t vc_load(const void *p) {
     return (int64_t)__hip_atomic_load(reinterpret_cast<const uint64_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -98,6 +97,29 @@ __global__ __launch_bounds__(kBlock) void vc_check_kernel(int64_t n, const doubl
 
 static void vc_msg(psk_result *res, const char *m) { std::snprintf(res->msg, sizeof(res->msg), "%s", m); }
 
+// the loop's device words: [state][hist maxiter][tickets], then b and the output when they are the host's. The
+// history follows the state unaligned: the final host copy reads both as one contiguous range.
+struct VcWork {
+    VcState *st;
+    double *hist, *b, *out;
+    uint32_t *tick;
+};
+static void vc_layout(Carve &cv, int64_t n, int64_t maxiter, bool dev_io, VcWork &w) {
+    w.st = cv.take<VcState>(sizeof(VcState), 8);
+    w.hist = cv.take<double>((size_t)maxiter * 8, 8);
+    w.tick = cv.take<uint32_t>(kVcTickBytes);
+    w.b = dev_io ? nullptr : cv.take<double>((size_t)n * 8);
+    w.out = dev_io ? nullptr : cv.take<double>((size_t)n * 8);
+}
+void vcycle_layout_probe(int64_t n, int64_t maxiter, bool dev_io, std::vector<int64_t> *log, int64_t *bytes) {
+    Carve cv;
+    cv.log = log;
+    VcWork w;
+    vc_layout(cv, n, maxiter, dev_io, w);
+    bytes[0] = (int64_t)cv.off;
+    bytes[1] = 0;
+}
+
 }  // namespace psk
 
 using namespace psk;
@@ -125,60 +147,46 @@ extern "C" int psk_vcycle(const psk_prec *M, const double *b, double *xout, cons
     AmgLoop lp;
     PSK_TRY(amg_loop_view(M, &lp));
     const bool dev_io = loc == PSK_DEVICE;
-    // the loop's device words: [state][hist maxiter][tickets], then b and the output when they are the host's
-    const size_t off_hist = sizeof(VcState), off_tick = (off_hist + (size_t)maxiter * 8 + 255) / 256 * 256,
-                 off_b = off_tick + kVcTickBytes, vec = ((size_t)n * 8 + 255) / 256 * 256;
-    PSK_TRY(lp.work->ensure(off_b + (dev_io ? 0 : 2 * vec)));
-    char *wk = lp.work->as<char>();
-    VcState *st = reinterpret_cast<VcState *>(wk);
-    double *dhist = reinterpret_cast<double *>(wk + off_hist);
-    uint32_t *tick = reinterpret_cast<uint32_t *>(wk + off_tick);
-    double *out = dev_io ? xout : reinterpret_cast<double *>(wk + off_b + vec);
+    int64_t need[2];
+    vcycle_layout_probe(n, maxiter, dev_io, nullptr, need);
+    PSK_TRY(lp.work->ensure((size_t)need[0]));
+    Carve cv{lp.work->as<char>()};
+    VcWork w;
+    vc_layout(cv, n, maxiter, dev_io, w);
+    VcState *st = w.st;
+    double *dhist = w.hist, *out = dev_io ? xout : w.out;
+    uint32_t *tick = w.tick;
     SolveKit *kit;
     PSK_TRY(solve_kit(c, false, &kit));
-    volatile int64_t *hdone = kit->hmap;
-    const int64_t hgen = (int64_t)(++kit->solve_gen & 0x7FFFFF) << kStampGenShift;
-    *hdone = 0;
-    auto stamp = [&]() -> int64_t {   // a stamp of this solve only (its generation), 0 = none
-        const int64_t hv = *hdone;
-        return (hv & ~kStampMask) == hgen ? (hv & kStampMask) : 0;
-    };
+    StampPoll poll(kit);
 
     int rc = PSK_OK;
     auto body = [&]() -> int {
         const double *bd = b;
         if (!dev_io) {
-            double *wb = reinterpret_cast<double *>(wk + off_b);
-            PSK_TRY(to_device_vec(b, loc, n, wb, s));
-            bd = wb;
+            PSK_TRY(to_device_vec(b, loc, n, w.b, s));
+            bd = w.b;
         }
         PSK_HIP(hipEventRecord(kit->ev0, s));
         PSK_TRY(amg_loop_start(M, c, bd, s));                                            // ||b||^2, x = copy(b)  :63, :69
         if (flags & PSK_VCYCLE_X0_GIVEN) PSK_TRY(to_device_vec(xout, loc, n, lp.x, s));   // before `out` is written
         PSK_HIP(hipMemsetAsync(tick, 0, kVcTickBytes, s));
-        hipLaunchKernelGGL(vc_init_kernel, dim3(1), dim3(1), 0, s, lp.normb2, st, const_cast<int64_t *>(hdone), hgen);
+        hipLaunchKernelGGL(vc_init_kernel, dim3(1), dim3(1), 0, s, lp.normb2, st, poll.hdone(), poll.hgen());
         PSK_HIP(hipGetLastError());
         // the one wait in front of the loop: b = 0 runs no cycle (:64-65)
-        PSK_HIP(hipEventRecord(kit->fev[0], s));
-        PSK_HIP(hipEventSynchronize(kit->fev[0]));
-        const bool zero_b = stamp() == 1;
-        const int C = ctl->check_every > 0 ? ctl->check_every : 1, NS = kPollSlots;
+        PSK_TRY(poll.wait(s));
+        const bool zero_b = poll.stamp() == 1;
+        const int C = ctl->check_every > 0 ? ctl->check_every : 1;
         const dim3 gc((unsigned)((n + kBlock - 1) / kBlock));
         int64_t launched = 0;
         for (int64_t k = 0; k < maxiter && !zero_b; ++k) {
-            if (k > 0 && k % C == 0) {
-                const int64_t chunk = k / C;   // chunks fully enqueued
-                PSK_HIP(hipEventRecord(kit->fev[(chunk - 1) % NS], s));
-                if (chunk - 1 - kVcLag >= 0) {
-                    PSK_HIP(hipEventSynchronize(kit->fev[(chunk - 1 - kVcLag) % NS]));
-                    const int64_t v = stamp();
-                    if (v != 0 && v <= (chunk - kVcLag) * (int64_t)C + 1) break;
-                }
-            }
+            bool stop;
+            PSK_TRY(poll.step<kVcLag>(k, C, s, &stop));
+            if (stop) break;
             PSK_TRY(amg_cycle(M, c, bd, s));      // x = runCycle(b, x)  :81
             PSK_TRY(amg_residual(M, bd, s));      // r = b - A x, ||r||^2 in the same launch  :84, :87
             hipLaunchKernelGGL(vc_check_kernel, gc, dim3(kBlock), 0, s, n, lp.x, out, lp.sum, ctl->tau, st, tick, dhist, k,
-                               maxiter, const_cast<int64_t *>(hdone), hgen);
+                               maxiter, poll.hdone(), poll.hgen());
             PSK_HIP(hipGetLastError());
             launched = k + 1;
         }
@@ -187,7 +195,7 @@ extern "C" int psk_vcycle(const psk_prec *M, const double *b, double *xout, cons
         std::vector<double> host((size_t)(kVcStateWords + launched));
         int32_t *gs_word = reinterpret_cast<int32_t *>(static_cast<char *>(kit->hstage) + kStageBytes - 64);
         PSK_TRY(gridsum_check_enqueue(c, gs_word));
-        PSK_HIP(hipMemcpyAsync(host.data(), wk, host.size() * 8, hipMemcpyDeviceToHost, s));
+        PSK_HIP(hipMemcpyAsync(host.data(), st, host.size() * 8, hipMemcpyDeviceToHost, s));
         if (zero_b) PSK_HIP(hipMemsetAsync(out, 0, (size_t)n * 8, s));   // np.zeros_like(b)  :65
         if (!dev_io) PSK_TRY(from_device_vec(out, loc, n, xout, s));
         PSK_HIP(hipStreamSynchronize(s));
