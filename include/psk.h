@@ -336,6 +336,22 @@ int psk_pcg(const psk_csr *A, const psk_prec *M, const double *b, double *x, con
             psk_result *res, double *hist, int32_t loc);
 int psk_gmres(const psk_csr *A, const psk_prec *M, const double *b, double *x, const psk_ctl *ctl,
               psk_result *res, double *hist, int32_t loc);
+/* Right-preconditioned BiCGStab for nonsymmetric A (no reference counterpart: the reference's only nonsymmetric
+ * method is GMRES): about eight vectors and two SpMVs per iteration whatever the iteration count, no restart
+ * (ctl->restart is ignored). x0 = 0, every elementwise operation rounded once:
+ *   r = rhat = p = b; rho = rhat.r; per iteration k: v = A M^-1 p; alpha = rho / rhat.v; s = r - alpha v;
+ *   ||s|| <= tau*||b||: x += alpha M^-1 p, hist[k] = ||s||, stop (the half step). Else t = A M^-1 s;
+ *   omega = t.s / t.t; x = (x + alpha M^-1 p) + omega M^-1 s; r = s - omega t; hist[k] = ||r||; stop when
+ *   ||r|| <= tau*||b|| or k == maxiter-1 with !fail_on_maxiter; beta = (rhat.r / rho)(alpha / omega);
+ *   rho = rhat.r; p = r + beta (p - omega v).
+ * Stopping at iteration k: PSK_CONVERGED, iters = k+1, hist_len = k+1; on a tolerance exit (PSK_EXIT_TOLERANCE)
+ * resid = the true ||b - A x|| and resid_recursive the recursive one, PSK_TRUE_RESID_FAIL when the true one
+ * misses tau*||b|| (as psk_gmres). rhat.v, t.t, omega or rhat.r == 0 at iteration k: PSK_BREAKDOWN, iters = k
+ * (PSK_EXIT_DOT_BREAKDOWN). maxiter reached: PSK_MAXITER, iters = maxiter-1. b = 0: as psk_pcg. ctl->norm_b as for
+ * psk_gmres. spmv_launches counts the SpMV launches that did their work. A sharded A with more than one rank:
+ * PSK_ERR_UNSUPPORTED. */
+int psk_bicgstab(const psk_csr *A, const psk_prec *M, const double *b, double *x, const psk_ctl *ctl,
+                 psk_result *res, double *hist, int32_t loc);
 /* The standalone AMG V-cycle solver, AMGVCycleSolver.solve (VCycleSolver.py:52-95), on the device: M is a
  * PSK_PREC_AMG whose finest level matrix is the system matrix (PSK_ERR_ARG otherwise); its own num_iters and
  * tau are ignored, ctl->maxiter (> 0) and ctl->tau rule. x0 = copy(b) (:69), or the caller's x with

@@ -36,7 +36,8 @@ class IterativeLinearSolverType(LinearSolverType):
 class IterativeLinearSolver(LinearSolver, IterativeSolver):
     """Solver base (IterativeLinearSolver.py:60-86) + the device driver."""
 
-    _entry = None          # "psk_pcg" / "psk_gmres"
+    _entry = None          # "psk_pcg" / "psk_gmres" / "psk_bicgstab"
+    _method = "GMRES"      # the method's name in the true-residual failure text (GMRESSolver.py:167-174)
     # PCGSolver.solve prints 'prec frozen = ...' and 'building prec' on every solve with b != 0
     # (PCGSolver.py:91,93); PCGSolver sets this (class attribute: a driver may switch it off)
     _echo_setup = False
@@ -140,7 +141,7 @@ class IterativeLinearSolver(LinearSolver, IterativeSolver):
         N.check(fn(dA.handle, ph, N.ptr(bp), N.ptr(x), ctypes.byref(ctl), ctypes.byref(res), N.ptr(hist), loc),
                 self._entry)
         if custom and res.exit in (N.PSK_EXIT_TOLERANCE, N.PSK_EXIT_ARNOLDI_BREAKDOWN):
-            # GMRES stopped on its recursive residual: the true-residual test in the caller's norm
+            # GMRES / BiCGStab stopped on the recursive residual: the true-residual test in the caller's norm
             # (GMRESSolver.py:163-174): resid = b - A x on the device, its norm by the caller's code
             rt = _host_copy(b) - _host_copy(spmv(dA, x))
             nrt = float(self.norm(rt))
@@ -149,8 +150,8 @@ class IterativeLinearSolver(LinearSolver, IterativeSolver):
             res.status = N.PSK_CONVERGED if ok else N.PSK_TRUE_RESID_FAIL
             res.success = int(ok)
             res.msg = b"" if ok else (
-                "GMRES failure: true residual %12.5g did not meet tolerance tau=%12.5g. Recursive residual "
-                "was %12.5g." % (nrt, self.tau(), res.resid_recursive)).encode()
+                "%s failure: true residual %12.5g did not meet tolerance tau=%12.5g. Recursive residual "
+                "was %12.5g." % (self._method, nrt, self.tau(), res.resid_recursive)).encode()
         return self._to_status(res, x, hist[:res.hist_len])
 
     # -----------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """Drop-in for PySolvers.Linear's PCG/GMRES path (Linear/__init__.py:1-12 names)."""
 from .AMGPreconditioner import AMG, AMGPreconditioner
+from .BiCGStabSolver import BiCGStab, BiCGStabSolver
 from .ClassicSmoothers import ChebyshevSmoother, GaussSeidelSmoother, JacobiSmoother
 from .DeviceMatrix import DeviceCSR, DeviceVector, spmv
 from .DirectSolver import DefaultDirect, DefaultDirectSolver
