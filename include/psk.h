@@ -36,6 +36,9 @@
  *   psk_mm_*         scipy.io.mmread(path).tocsr() (examples/DHTestProblem.py:27-28).
  *   psk_sa_aggregate BuildAggregates + BuildFilteredMatrix (SmoothedAggregation.py:57-183),
  *                    O(nnz) host code.
+ *   psk_csr_matmat, psk_csr_transpose, psk_sa_prolongator: the scipy products, transpose and numpy
+ *                    smoothing lines of the AMG setup (SmoothedAggregation.py:185-205,
+ *                    MLHierarchy.py:283-322) on the device, same bits in the same stored order.
  */
 #ifndef PSK_H
 #define PSK_H
@@ -325,6 +328,32 @@ int psk_csr_create_mm(const char *path, psk_csr **out);
  * causes). tol is the strength threshold (0.08 * 0.5^(lvl-1) by default). */
 int psk_sa_aggregate(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, double tol,
                      int32_t *agg, int64_t *count, double *af_vals);
+
+/* ---- sparse operator construction on the device (spgemm.hip) --------------------------------- */
+/* C = A B for an (m x k) A and a (k x n) B, both on the device: scipy's csr_matmat (`A @ B`), bit for bit and in
+ * its stored entry order. For output row i enumerate the products t = 0, 1, ...: the entries jj of A's row i in
+ * stored order and, for each, the entries kk of B's row A.col[jj] in stored order; product t is the rounded
+ * A.val[jj] * B.val[kk] (a separate multiply and add, no FMA) on column B.col[kk]; a column's value is
+ * ((0.0 + p_a) + p_b) + ... over its products in ascending t; the columns are emitted in DESCENDING order of their
+ * first t and a column whose sum == 0.0 is dropped. Duplicate columns inside a row of A or B, unsorted rows,
+ * explicit zeros and empty rows need no special case. The result ends like psk_csr_create(..., PSK_DEVICE) (the
+ * SpMV layout choice applies) and may be rectangular. PSK_ERR_ARG: inner dimensions differ. PSK_ERR_UNSUPPORTED:
+ * a sharded operand, a result over the int32 nnz limit, or a row with more than PSK_SPGEMM_ROW_CAP products.
+ * *C is written only on success. The result does not depend on the launch geometry. */
+#define PSK_SPGEMM_ROW_CAP 1024
+int psk_csr_matmat(const psk_csr *A, const psk_csr *B, psk_csr **C);
+/* A.transpose().tocsr() on the device: row j of the result holds A's entries of column j in ascending source
+ * row and, within one source row, in stored order (duplicates kept; deterministic). PSK_ERR_UNSUPPORTED: a
+ * sharded operand. */
+int psk_csr_transpose(const psk_csr *A, psk_csr **At);
+/* SA_coarsen's lines after the aggregation (SmoothedAggregation.py:185-229) from psk_sa_aggregate's outputs:
+ * P = S Phat with S on A's structure, s = omega * af_vals[e], v = s / d[row], S[e] = col == row ? 1 - v : -v
+ * (every operation rounded once, IEEE division), d[row] = the sum of the row's stored diagonal entries in
+ * stored order from 0.0 (scipy's diagonal()), Phat's row i = the single entry (agg[i], 1.0), n x count, and the
+ * product as psk_csr_matmat. agg[n] and af_vals[nnz] live where loc says. PSK_ERR_ARG: A not square, an
+ * aggregate outside [0, count) (checked for PSK_HOST). */
+int psk_sa_prolongator(const psk_csr *A, const int32_t *agg, int64_t count, const double *af_vals, double omega,
+                       int32_t loc, psk_csr **P);
 
 /* ---- solvers ------------------------------------------------------------------------------ */
 /* M == NULL means identity. b, x: length n (local length for a distributed A); with loc ==

@@ -16,8 +16,14 @@ instead of a sparse triangular-solve chain thousands of dependency levels deep (
 coarse="lu" keeps SuperLU's factors of A_0 computed once on the host as two device triangular solves.
 "auto" (default) takes the dense inverse up to 32,768 unknowns and falls back to the factors when the
 inverse cannot be formed (A_0 singular, rocSOLVER absent).
+
+setup="device" (default "host") builds P, R and every coarse A_k in HBM (SmoothedAggregation.py,
+pysolvers_amd/csrc/spgemm.hip: the same bits in the same stored entry order) and hands those handles straight to
+psk_prec_create_amg, with no re-upload; the host copies the smoothers and the coarse factorisation read are
+downloaded on first use.
 """
 import ctypes
+import time
 
 import numpy as np
 import scipy.sparse as sp
@@ -28,13 +34,14 @@ from .ClassicSmoothers import GaussSeidelSmoother, _Smoother
 from .DeviceMatrix import DeviceCSR
 from .Preconditioner import DeviceOperator, GenericPreconditioner
 from .PreconditionerType import PreconditionerType
-from .SmoothedAggregation import SmoothedAggregationMLHierarchy
+from .SmoothedAggregation import SmoothedAggregationMLHierarchy, check_setup
 from .TriangularSolve import superlu_transposed_solver
 
 
 class AMG(PreconditionerType):
     def __init__(self, numIters=5, numLevels=2, nuPre=2, nuPost=2, smoother=GaussSeidelSmoother, coarse="auto",
-                 coarse_refine=0):
+                 coarse_refine=0, setup="host"):
+        self.setup = check_setup(setup)
         self.numIters = numIters
         self.numLevels = numLevels
         self.nuPre = nuPre
@@ -46,7 +53,7 @@ class AMG(PreconditionerType):
     def form(self, A):
         return AMGPreconditioner(A, numIters=self.numIters, numLevels=self.numLevels, nuPre=self.nuPre,
                                  nuPost=self.nuPost, smoother=self.smoother, coarse=self.coarse,
-                                 coarse_refine=self.coarse_refine)
+                                 coarse_refine=self.coarse_refine, setup=self.setup)
 
 
 def coarse_factor(A_c):
@@ -92,23 +99,39 @@ class AMGPreconditioner(DeviceOperator, GenericPreconditioner):
     device_kind = N.PSK_PREC_AMG
 
     def __init__(self, A, numIters=5, numLevels=2, nuPre=2, nuPost=2, smoother=GaussSeidelSmoother, tau=1.0e-8,
-                 coarse="auto", coarse_refine=None):
+                 coarse="auto", coarse_refine=None, setup="host"):
+        check_setup(setup)
         if not (isinstance(smoother, type) and issubclass(smoother, _Smoother) and smoother is not _Smoother):
             raise TypeError("AMG smoother must be a smoother class with a device operator: GaussSeidelSmoother, "
                             "JacobiSmoother, ChebyshevSmoother or ChebyshevSmoother.of(...)")
         if coarse not in ("auto", "dense", "lu"):
             raise ValueError("AMG coarse must be 'auto', 'dense' or 'lu'")
+        t0 = time.perf_counter()
         dA = A if isinstance(A, DeviceCSR) else DeviceCSR.from_scipy(A)
         Ah = A.to_scipy() if isinstance(A, DeviceCSR) else sp.csr_matrix(A)
+        t_fine = time.perf_counter() - t0
         self.n = Ah.shape[0]
         self.numIters, self.numLevels, self.nuPre, self.nuPost = numIters, numLevels, nuPre, nuPost
-        self.mlh = SmoothedAggregationMLHierarchy(Ah, numLevels=numLevels)
+        self.setup = setup
+        # seconds of form()'s phases after the hierarchy's own (mlh.setup_stats["seconds"]); tools/amg_setup_ab.py
+        self.setup_seconds = dict(fine=t_fine, hierarchy=0.0, upload=0.0, smoothers=0.0, coarse=0.0)
+        t0 = time.perf_counter()
+        self.mlh = SmoothedAggregationMLHierarchy(Ah, numLevels=numLevels, setup=setup,
+                                                  device_A=dA if setup == "device" else None)
+        t1 = time.perf_counter()
         L = numLevels
-        # device copies; the finest level is the caller's matrix
-        self._A = [DeviceCSR.from_scipy(self.mlh.matrix(k)) for k in range(L - 1)] + [dA]
-        self._P = [DeviceCSR.from_scipy(self.mlh.update(k), rectangular=True) for k in range(L - 1)]
-        self._R = [DeviceCSR.from_scipy(self.mlh.downdate(k), rectangular=True) for k in range(L - 1)]
+        if setup == "device":   # the handles the hierarchy built; the finest level is the caller's matrix
+            self._A = [self.mlh.device_matrix(k) for k in range(L - 1)] + [dA]
+            self._P = [self.mlh.device_update(k) for k in range(L - 1)]
+            self._R = [self.mlh.device_downdate(k) for k in range(L - 1)]
+        else:                   # device copies; the finest level is the caller's matrix
+            self._A = [DeviceCSR.from_scipy(self.mlh.matrix(k)) for k in range(L - 1)] + [dA]
+            self._P = [DeviceCSR.from_scipy(self.mlh.update(k), rectangular=True) for k in range(L - 1)]
+            self._R = [DeviceCSR.from_scipy(self.mlh.downdate(k), rectangular=True) for k in range(L - 1)]
+        t2 = time.perf_counter()
         self._S = [None] + [smoother(self.mlh.matrix(k), device_A=self._A[k]) for k in range(1, L)]
+        t3 = time.perf_counter()
+        self.setup_seconds.update(hierarchy=t1 - t0, upload=t2 - t1, smoothers=t3 - t2)
         if any(getattr(getattr(s, "operator", None), "device_handle", None) is None for s in self._S[1:]):
             raise TypeError("AMG smoother %s provides no device operator" % smoother.__name__)
         self._coarse, self._lu, self.coarse_kind = None, None, "lu"
@@ -127,6 +150,7 @@ class AMGPreconditioner(DeviceOperator, GenericPreconditioner):
                     raise
         if self._coarse is None:
             self._coarse, self._lu = coarse_solver(self.mlh.matrix(0))
+        self.setup_seconds["coarse"] = time.perf_counter() - t3
         pa, ka = N.handle_array([d.handle for d in self._A])
         pp, kp = N.handle_array([d.handle for d in self._P])
         pr, kr = N.handle_array([d.handle for d in self._R])

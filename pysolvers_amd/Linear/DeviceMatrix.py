@@ -158,6 +158,22 @@ class DeviceCSR:
                                      None), "psk_csr_layout")
         return slots.value, packed.value
 
+    @classmethod
+    def _adopt(cls, h, ncols):
+        """A handle the library built on the device (psk_csr_matmat / psk_csr_transpose / psk_sa_prolongator)."""
+        n, nnz = N.I64(), N.I64()
+        N.check(N.lib.psk_csr_info(h, ctypes.byref(n), ctypes.byref(nnz)), "psk_csr_info")
+        return cls(h, n.value, nnz.value, ncols=ncols)
+
+    def transpose(self):
+        """A^T as a DeviceCSR, built on the device (psk_csr_transpose): ``A.transpose().tocsr()`` — row j holds
+        A's entries of column j in ascending source row, stored order inside one row, duplicates kept."""
+        if self.comm is not None:
+            raise ValueError("transpose of a sharded matrix is not supported")
+        h = ctypes.c_void_p()
+        N.check(N.lib.psk_csr_transpose(self._h, ctypes.byref(h)), "psk_csr_transpose")
+        return DeviceCSR._adopt(h, self.n)
+
     def to_scipy(self):
         indptr = np.empty(self.n + 1, dtype=np.int32)
         indices = np.empty(self.nnz, dtype=np.int32)
@@ -182,6 +198,21 @@ def as_device_matrix(A):
     if isinstance(A, DeviceCSR):
         return A
     return DeviceCSR.from_scipy(A)
+
+
+def matmat(A, B):
+    """C = A B as a DeviceCSR, built on the device (psk_csr_matmat): the bits and the stored entry order of scipy's
+    ``A @ B`` for the same stored arrays. scipy operands are uploaded first. Raises PskError with code
+    PSK_ERR_UNSUPPORTED when a row has more than PSK_SPGEMM_ROW_CAP products."""
+    dA = A if isinstance(A, DeviceCSR) else DeviceCSR.from_scipy(A, rectangular=True)
+    dB = B if isinstance(B, DeviceCSR) else DeviceCSR.from_scipy(B, rectangular=True)
+    if dA.comm is not None or dB.comm is not None:
+        raise ValueError("matmat of a sharded matrix is not supported")
+    if dA.ncols != dB.n:
+        raise ValueError("dimension mismatch")
+    h = ctypes.c_void_p()
+    N.check(N.lib.psk_csr_matmat(dA.handle, dB.handle, ctypes.byref(h)), "psk_csr_matmat")
+    return DeviceCSR._adopt(h, dB.ncols)
 
 
 def spmv(A, x):

@@ -21,17 +21,32 @@ import numpy as np
 from .. import _native as N
 from ..IterativeSolver import CommonSolverArgs
 from .AMGPreconditioner import AMGPreconditioner
+from .SmoothedAggregation import check_setup
 from .ClassicSmoothers import GaussSeidelSmoother
 from .DeviceMatrix import DeviceVector, spmv
 from .IterativeLinearSolver import (IterativeLinearSolver, IterativeLinearSolverType, _host_copy, _is_zero_norm,
                                     _like)
 
 
-class AMGVCycle(IterativeLinearSolverType):
+class _TakesSetup(type(IterativeLinearSolver)):
+    """The product-only keyword ``setup="host" | "device"`` (where the AMG hierarchy is built, AMGPreconditioner.py)
+    of the two classes below. Their ``__init__`` signatures stay the reference's, parameter for parameter
+    (tests/test_vcycle_api.py pins them against it), so the keyword is taken by the class call:
+    ``AMGVCycle(control, numLevels=3, setup="device")``. Anything but "host" or "device" raises ValueError."""
+
+    def __call__(cls, *args, setup="host", **kwargs):
+        check_setup(setup)
+        obj = super().__call__(*args, **kwargs)
+        obj.setup = setup
+        return obj
+
+
+class AMGVCycle(IterativeLinearSolverType, metaclass=_TakesSetup):
 
     def __init__(self, control=CommonSolverArgs(), numLevels=2, nuPre=2, nuPost=2, smoother=GaussSeidelSmoother,
                  name='AMGVCycle'):
         super().__init__(control=control, precond=None)          # VCycleSolver.py:20 (name not passed on)
+        self.setup = "host"                                      # _TakesSetup: where the hierarchy is built
         self.numLevels = numLevels
         self.nuPre = nuPre
         self.nuPost = nuPost
@@ -41,15 +56,16 @@ class AMGVCycle(IterativeLinearSolverType):
         """Creates an AMG V-cycle solver object with the specified parameters (VCycleSolver.py:26-36)."""
         return AMGVCycleSolver(name=self.name() if name is None else name, control=self.control(),
                                numLevels=self.numLevels, nuPre=self.nuPre, nuPost=self.nuPost,
-                               smoother=self.smoother)
+                               smoother=self.smoother, setup=self.setup)
 
 
-class AMGVCycleSolver(IterativeLinearSolver):
+class AMGVCycleSolver(IterativeLinearSolver, metaclass=_TakesSetup):
     _entry = "psk_vcycle"
 
     def __init__(self, control=CommonSolverArgs(), numLevels=2, nuPre=2, nuPost=2, smoother=GaussSeidelSmoother,
                  name='AMGVCycle'):
         super().__init__(control=control, name=name, precond=None)
+        self.setup = "host"        # _TakesSetup: "host" / "device", where the hierarchy is built
         self.numLevels = numLevels
         self.nuPre = nuPre
         self.nuPost = nuPost
@@ -77,7 +93,8 @@ class AMGVCycleSolver(IterativeLinearSolver):
         if self._cycleMgr is None or not self.matrixFrozen():  # :71-76
             # numIters and tau are the preconditioner apply's; psk_vcycle takes its own from the control
             self._cycleMgr = AMGPreconditioner(dA, numIters=1, numLevels=self.numLevels, nuPre=self.nuPre,
-                                               nuPost=self.nuPost, smoother=self.smoother, tau=0.0)
+                                               nuPost=self.nuPost, smoother=self.smoother, tau=0.0,
+                                               setup=self.setup)
         if custom:
             return self._host_norm_vcycle(dA, b, normB)
         maxiter = int(self.maxiter())

@@ -2,7 +2,7 @@
 from .AMGPreconditioner import AMG, AMGPreconditioner
 from .BiCGStabSolver import BiCGStab, BiCGStabSolver
 from .ClassicSmoothers import ChebyshevSmoother, GaussSeidelSmoother, JacobiSmoother
-from .DeviceMatrix import DeviceCSR, DeviceVector, spmv
+from .DeviceMatrix import DeviceCSR, DeviceVector, matmat, spmv
 from .DirectSolver import DefaultDirect, DefaultDirectSolver
 from .Distributed import Communicator, fd_laplacian_2d_sharded, halo_cols, shard_csr
 from .GMRESSolver import GMRES, GMRESSolver

@@ -23,6 +23,7 @@ PSK_VCYCLE_X0_GIVEN = 1   # psk_vcycle flags: x holds the starting iterate
 PSK_PREC_IDENTITY, PSK_PREC_JACOBI, PSK_PREC_ILU, PSK_PREC_AMG, PSK_PREC_DENSE, PSK_PREC_CHEBYSHEV = 0, 1, 2, 3, 4, 5
 PSK_LAYOUT_CSR, PSK_LAYOUT_SLICED, PSK_LAYOUT_SLICED_WIDE, PSK_LAYOUT_SLICED_DICT, PSK_LAYOUT_DIAG = 0, 1, 2, 3, 4
 PSK_UNIQUE_ID_BYTES = 128
+PSK_SPGEMM_ROW_CAP = 1024   # psk_csr_matmat: products of one output row
 
 STATUS_NAMES = {PSK_CONVERGED: "converged", PSK_MAXITER: "maxiter", PSK_BREAKDOWN: "breakdown",
                 PSK_TRUE_RESID_FAIL: "true residual above tolerance"}
@@ -91,6 +92,9 @@ SIGNATURES = {
     "psk_mm_read": (ctypes.c_int, [ctypes.c_char_p, P, P, P, ctypes.POINTER(I64)]),
     "psk_csr_create_mm": (ctypes.c_int, [ctypes.c_char_p, PP]),
     "psk_sa_aggregate": (ctypes.c_int, [I64, P, P, P, F64, P, ctypes.POINTER(I64), P]),
+    "psk_csr_matmat": (ctypes.c_int, [P, P, PP]),
+    "psk_csr_transpose": (ctypes.c_int, [P, PP]),
+    "psk_sa_prolongator": (ctypes.c_int, [P, P, I64, P, F64, I32, PP]),
     "psk_pcg": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_gmres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_bicgstab": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),

@@ -101,6 +101,46 @@ static void csr_free(psk_csr *A) {
     A->peers.clear();
 }
 
+namespace psk {
+
+// A device-built matrix (spgemm.hip): the handle with its three arrays allocated and nothing in them, then —
+// once the kernels that fill them are queued on s — the end of every creation path (the SpMV layout choice).
+int csr_new_device(int64_t n, int64_t ncols, int64_t nnz, psk_csr **out) {
+    if (nnz > kMaxNnz || n >= INT32_MAX || ncols >= INT32_MAX)
+        return fail(PSK_ERR_UNSUPPORTED, "int32 CSR indices required (nnz < 2^31 - 1536)");
+    Context *c;
+    PSK_TRY(ctx(&c));
+    psk_csr *A = new psk_csr();
+    A->n = n;
+    A->ncols = ncols;
+    A->nnz = nnz;
+    A->tile_rows = tile_rows_for(n, nnz);
+    A->n_global = n;
+    A->row_begin = 0;
+    A->row_end = n;
+    A->device = c->device;
+    const int rc = csr_alloc(A, n, nnz);
+    if (rc != PSK_OK) {
+        csr_discard(A);
+        return rc;
+    }
+    *out = A;
+    return PSK_OK;
+}
+
+int csr_finish_device(psk_csr *A, hipStream_t s) {
+    PSK_HIP(hipStreamSynchronize(s));
+    return csr_choose_layout(A, s);
+}
+
+void csr_discard(psk_csr *A) {
+    if (!A) return;
+    csr_free(A);
+    delete A;
+}
+
+}  // namespace psk
+
 extern "C" {
 
 int psk_csr_create(int64_t n, int64_t nnz, const int32_t *rowptr, const int32_t *colidx,

@@ -991,6 +991,12 @@ int tile_rows_for(int64_t n, int64_t nnz);
 // SpMV layout of a freshly created matrix: the sliced copy when it streams no more bytes than the
 // CSR arrays (PSK_SPMV_LAYOUT=csr|sliced overrides); called at the end of every creation path
 int csr_choose_layout(psk_csr *A, hipStream_t s);
+// a matrix whose arrays the device fills (csr.hip; spgemm.hip's results): the handle with rowptr[n+1], colidx[nnz]
+// and vals[nnz] allocated; csr_finish_device drains s and ends like every creation path (csr_choose_layout);
+// csr_discard releases a handle that is not handed out
+int csr_new_device(int64_t n, int64_t ncols, int64_t nnz, psk_csr **out);
+int csr_finish_device(psk_csr *A, hipStream_t s);
+void csr_discard(psk_csr *A);
 // one-shot SpMV (grid = tiles of A->tile_rows rows); dot modes write their grid sum to partial[0].
 // ev0/ev1 (optional): HIP events the dispatch itself records at the kernel's start and end
 // (hipExtLaunchKernel), so their interval is the kernel alone, without the launch gaps around it
