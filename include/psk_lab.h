@@ -89,6 +89,22 @@ int psk_lab_pcg_flush(int64_t n, int64_t k, int32_t stag, double *x, const doubl
 #define PSK_LAB_LAYOUT_DEV_IO 4 /* V-cycle: b and x are the caller's device vectors (not staged) */
 int psk_lab_solver_layout(int32_t solver, int64_t n, int64_t ncols, int64_t maxiter, int64_t restart, int32_t flags,
                           int32_t P, int64_t *offsets, int32_t *count, int64_t *bytes);
+/* Tests of the GMRES Arnoldi kernels (tests/test_gpu_gmres_arnoldi.py): what the last psk_gmres on matrix A left in
+ * its workspace. psk_gmres carves A's two workspace buffers with one layout function and the buffers stay on the
+ * matrix after the solve; this carves them again for the same maxiter, restart and gen (1: a general preconditioner,
+ * one that is neither none nor Jacobi), waits for the library stream and copies to host arrays, any of which may be
+ * NULL. With K = the basis of one cycle (restart, or maxiter when it is 0 or larger): Q = the first `cols` basis
+ * vectors of the last cycle, n x cols column-major (the padded column stride removed); H = the unrotated Hessenberg
+ * columns and R = the rotated ones, (K+1) x K column-major; CS[2K] = the rotations (c, s); g[K+1]; y[K+1] = the last
+ * least-squares solution; state[6] = done, brk, kconv, normB, tauNormB, rec of the solve's device state. In a
+ * restarted solve H, R, CS and g hold the last cycle's columns on top of what earlier cycles left beyond them.
+ * PSK_ERR_ARG when either buffer is smaller than that layout needs or cols > K+1. It reads only.
+ * psk_lab_gmres_prefill: psk_gmres never clears its basis or its rotations, so a test of what the kernels leave
+ * untouched (the columns after a breakdown or after convergence) first grows A's two buffers to what that solve will
+ * ask for and sets every byte of both to `byte`; the solve then keeps the buffers. */
+int psk_lab_gmres_internals(const psk_csr *A, int64_t maxiter, int32_t restart, int32_t gen, int32_t cols, double *Q,
+                            double *H, double *R, double *CS, double *g, double *y, double *state);
+int psk_lab_gmres_prefill(psk_csr *A, int64_t maxiter, int32_t restart, int32_t gen, int32_t byte);
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,8 @@ LAB_SIGNATURES = {
     "psk_lab_pcg_flush": (ctypes.c_int, [I64, I64, I32, P, P, P]),
     "psk_lab_solver_layout": (ctypes.c_int, [I32, I64, I64, I64, I64, I32, I32, ctypes.POINTER(I64),
                                             ctypes.POINTER(I32), ctypes.POINTER(I64)]),
+    "psk_lab_gmres_internals": (ctypes.c_int, [P, I64, I32, I32, I32, P, P, P, P, P, P, P]),
+    "psk_lab_gmres_prefill": (ctypes.c_int, [P, I64, I32, I32, I32]),
 }
 _lab = None
 

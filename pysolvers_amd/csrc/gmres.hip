@@ -268,6 +268,44 @@ void gmres_layout_probe(int64_t n, int64_t maxiter, int64_t restart, bool gen, s
     bytes[0] = (int64_t)big.off;
     bytes[1] = (int64_t)sm.off;
 }
+// the regions psk_gmres(maxiter, restart, gen) carved on this matrix: the same gm_layout over A->ws / A->ws_small.
+// grow: size the two buffers as the solve would (a later solve then keeps them); otherwise PSK_ERR_ARG when either
+// is smaller than that layout. Host code only (psk_lab_gmres_internals, psk_lab_gmres_prefill).
+int gmres_work_view(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool grow, GmresView *v) {
+    if (!A || !v || maxiter < 0 || restart < 0 || A->n < 0) return fail(PSK_ERR_ARG, "gmres_work_view: bad arguments");
+    int64_t need[2];
+    gmres_layout_probe(A->n, maxiter, restart, gen, nullptr, need);
+    if (grow) {
+        PSK_TRY(A->ws.ensure((size_t)need[0]));
+        PSK_TRY(A->ws_small.ensure((size_t)need[1]));
+    }
+    if (!A->ws.p || !A->ws_small.p || A->ws.bytes < (size_t)need[0] || A->ws_small.bytes < (size_t)need[1])
+        return fail(PSK_ERR_ARG, "gmres_work_view: the matrix's workspace is smaller than this layout");
+    Carve big{A->ws.as<char>()}, sm{A->ws_small.as<char>()};
+    GmresWork w;
+    const int64_t K = gm_basis(maxiter, restart);
+    gm_layout(big, sm, A->n, maxiter, K, gen, w);
+    v->n = A->n;
+    v->K = K;
+    v->ldq = (int64_t)((((size_t)A->n * 8 + 255) / 256 * 256) / 8);
+    v->Q = w.Q;
+    v->H = w.H;
+    v->R = w.R;
+    v->CS = w.CS;
+    v->g = w.g;
+    v->dy = w.dy;
+    v->done = &w.st->done;
+    v->brk = &w.st->brk;
+    v->kconv = &w.st->kconv;
+    v->normB = &w.st->normB;
+    v->tauNormB = &w.st->tauNormB;
+    v->rec = &w.st->rec;
+    v->big = A->ws.p;
+    v->big_bytes = (size_t)need[0];
+    v->small = A->ws_small.p;
+    v->small_bytes = (size_t)need[1];
+    return PSK_OK;
+}
 
 }  // namespace psk
 

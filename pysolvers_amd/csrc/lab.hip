@@ -5,6 +5,7 @@
 // product path calls them.
 #include "trisolve.hpp"
 #include "pcg_state.hpp"
+#include "solve_loop.hpp"
 #include "../../include/psk_lab.h"
 
 #include <chrono>
@@ -355,5 +356,55 @@ extern "C" int psk_lab_solver_layout(int32_t solver, int64_t n, int64_t ncols, i
     if ((size_t)*count < log.size()) return fail(PSK_ERR_ARG, "psk_lab_solver_layout: offsets too short");
     *count = (int32_t)log.size();
     for (size_t i = 0; i < log.size(); ++i) offsets[i] = log[i];
+    return PSK_OK;
+}
+
+// ---- psk_gmres's workspace after a solve (gmres.hip gmres_work_view): what the Arnoldi kernels left in HBM ----
+extern "C" int psk_lab_gmres_internals(const psk_csr *A, int64_t maxiter, int32_t restart, int32_t gen, int32_t cols,
+                                       double *Q, double *H, double *R, double *CS, double *g, double *y,
+                                       double *state) {
+    using namespace psk;
+    if (!A || cols < 0) return fail(PSK_ERR_ARG, "psk_lab_gmres_internals: bad arguments");
+    GmresView v;
+    PSK_TRY(gmres_work_view(const_cast<psk_csr *>(A), maxiter, restart, gen != 0, false, &v));
+    if (cols > v.K + 1) return fail(PSK_ERR_ARG, "psk_lab_gmres_internals: more columns than the basis holds");
+    Context *c;
+    PSK_TRY(ctx(&c));
+    PSK_HIP(hipStreamSynchronize(c->stream));
+    const size_t K = (size_t)v.K, ld = K + 1;
+    if (Q && cols > 0 && v.n > 0)   // n x cols, the padded column stride removed
+        PSK_HIP(hipMemcpy2D(Q, (size_t)v.n * 8, v.Q, (size_t)v.ldq * 8, (size_t)v.n * 8, (size_t)cols,
+                            hipMemcpyDeviceToHost));
+    if (H) PSK_HIP(hipMemcpy(H, v.H, ld * K * 8, hipMemcpyDeviceToHost));
+    if (R) PSK_HIP(hipMemcpy(R, v.R, ld * K * 8, hipMemcpyDeviceToHost));
+    if (CS) PSK_HIP(hipMemcpy(CS, v.CS, 2 * K * 8, hipMemcpyDeviceToHost));
+    if (g) PSK_HIP(hipMemcpy(g, v.g, ld * 8, hipMemcpyDeviceToHost));
+    if (y) PSK_HIP(hipMemcpy(y, v.dy, ld * 8, hipMemcpyDeviceToHost));
+    if (state) {
+        int32_t iv[3];
+        PSK_HIP(hipMemcpy(&iv[0], v.done, 4, hipMemcpyDeviceToHost));
+        PSK_HIP(hipMemcpy(&iv[1], v.brk, 4, hipMemcpyDeviceToHost));
+        PSK_HIP(hipMemcpy(&iv[2], v.kconv, 4, hipMemcpyDeviceToHost));
+        for (int i = 0; i < 3; ++i) state[i] = (double)iv[i];
+        PSK_HIP(hipMemcpy(&state[3], v.normB, 8, hipMemcpyDeviceToHost));
+        PSK_HIP(hipMemcpy(&state[4], v.tauNormB, 8, hipMemcpyDeviceToHost));
+        PSK_HIP(hipMemcpy(&state[5], v.rec, 8, hipMemcpyDeviceToHost));
+    }
+    return PSK_OK;
+}
+
+// psk_gmres does not clear its basis or its rotations (each is written before it is read): a test of what the kernels
+// leave untouched sets both buffers to a known byte first, sized as the solve will size them, so the solve keeps them
+extern "C" int psk_lab_gmres_prefill(psk_csr *A, int64_t maxiter, int32_t restart, int32_t gen, int32_t byte) {
+    using namespace psk;
+    if (!A || byte < 0 || byte > 255) return fail(PSK_ERR_ARG, "psk_lab_gmres_prefill: bad arguments");
+    Context *c;
+    PSK_TRY(ctx(&c));
+    PSK_HIP(hipStreamSynchronize(c->stream));   // a solve still queued on this matrix keeps its workspace
+    GmresView v;
+    PSK_TRY(gmres_work_view(A, maxiter, restart, gen != 0, true, &v));
+    PSK_HIP(hipMemsetAsync(v.big, byte, v.big_bytes, c->stream));
+    PSK_HIP(hipMemsetAsync(v.small, byte, v.small_bytes, c->stream));
+    PSK_HIP(hipStreamSynchronize(c->stream));
     return PSK_OK;
 }

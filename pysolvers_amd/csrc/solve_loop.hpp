@@ -26,6 +26,18 @@ void pcg_layout_probe(int64_t n, int64_t ncols, int64_t maxiter, bool gen, bool 
 void gmres_layout_probe(int64_t n, int64_t maxiter, int64_t restart, bool gen, std::vector<int64_t> *log, int64_t *bytes);
 void vcycle_layout_probe(int64_t n, int64_t maxiter, bool dev_io, std::vector<int64_t> *log, int64_t *bytes);
 
+// psk_gmres's workspace as the lab library reads it after a solve (gmres.hip gmres_work_view): device pointers
+// into the matrix's two buffers. Q: K + 1 columns of stride ldq doubles; H, R: (K + 1) x K column-major.
+struct GmresView {
+    int64_t n, K, ldq;
+    double *Q, *H, *R, *CS, *g, *dy;
+    const int32_t *done, *brk, *kconv;
+    const double *normB, *tauNormB, *rec;
+    void *big, *small;  // the two buffers and the bytes of each this layout covers
+    size_t big_bytes, small_bytes;
+};
+int gmres_work_view(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool grow, GmresView *v);
+
 // The done stamp (set_done, pcg_state.hpp; vc_check_kernel): k + 2 for a kernel of iteration k, 1 for the init
 // (0 = running) — a system-scope store to a host-mapped word, drained before the kernel ends, so once an event
 // recorded after this kernel has completed the host reads the word directly, with no per-chunk device-to-host

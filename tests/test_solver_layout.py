@@ -143,3 +143,12 @@ def test_rejects_bad_arguments():
     assert lab.psk_lab_solver_layout(PCG, 1, 1, 1, 0, 0, 0, off, ctypes.byref(cnt), nbytes) != 0
     cnt = N.I32(2)
     assert lab.psk_lab_solver_layout(PCG, 1, 1, 1, 0, 0, 1, off, ctypes.byref(cnt), nbytes) != 0
+
+
+def test_gmres_workspace_view_rejects_bad_arguments():
+    """psk_lab_gmres_internals / psk_lab_gmres_prefill carve a matrix's buffers with the layout above; without a
+    matrix (or with a negative size) they return PSK_ERR_ARG before any GPU call."""
+    lab = N.load_lab()
+    none = [None] * 7
+    assert lab.psk_lab_gmres_internals(None, 10, 0, 0, 1, *none) == N.PSK_ERR_ARG
+    assert lab.psk_lab_gmres_prefill(None, 10, 0, 0, 0) == N.PSK_ERR_ARG
