@@ -39,6 +39,8 @@
  *   psk_csr_matmat, psk_csr_transpose, psk_sa_prolongator: the scipy products, transpose and numpy
  *                    smoothing lines of the AMG setup (SmoothedAggregation.py:185-205,
  *                    MLHierarchy.py:283-322) on the device, same bits in the same stored order.
+ *   psk_csr_ilu0, psk_prec_create_ilu0: ILU(0) factored on the device; no reference counterpart (the
+ *                    reference's incomplete factors are SuperLU's).
  */
 #ifndef PSK_H
 #define PSK_H
@@ -354,6 +356,30 @@ int psk_csr_transpose(const psk_csr *A, psk_csr **At);
  * aggregate outside [0, count) (checked for PSK_HOST). */
 int psk_sa_prolongator(const psk_csr *A, const int32_t *agg, int64_t count, const double *af_vals, double omega,
                        int32_t loc, psk_csr **P);
+
+/* ---- ILU(0) on the device (ilu0.hip) ----------------------------------------------------------- */
+/* F = the ILU(0) factors of a square A on the device, in one matrix with A's pattern and its rows in ascending
+ * column order. A has at most one stored entry per (row, column) and a stored diagonal entry in every row; its rows
+ * may be stored in any order (they are sorted into the working copy first). With v = the values of that copy, for
+ * i = 0 .. n-1: for each entry e of row i with column k < i, in ascending k: l = v[e] / v[diag(k)] (IEEE division;
+ * row k is final by then), v[e] = l, and for each entry f of row k with column j > k, in ascending j, if row i stores
+ * column j at q: v[q] = v[q] - l * v[f] (the product rounded, then the difference: no FMA); then row i's pivot
+ * v[diag(i)] is in error when it is 0.0 or not finite. L = strict-lower(F) with a unit diagonal, U = upper(F) with
+ * the diagonal. The numeric phase runs one launch per dependency level of strict-lower(A) (the levels by the host
+ * planner of the triangular solves, from the downloaded pattern); every value receives its updates in ascending k,
+ * so the result does not depend on the launch geometry. The result ends like psk_csr_create(..., PSK_DEVICE) and
+ * psk_csr_download reads it back. PSK_ERR_ARG: A not square or empty, a column outside [0, n), a row without a
+ * stored diagonal entry, a zero or non-finite pivot (psk_last_error names the smallest such row).
+ * PSK_ERR_UNSUPPORTED: a sharded A, a duplicate column within a row. *F is written only on success. A is only
+ * read; nothing of it is borrowed. Replaces nothing in the reference (its incomplete factors are SuperLU's,
+ * ILUTPreconditioner.py:51-53). */
+int psk_csr_ilu0(const psk_csr *A, psk_csr **F);
+/* The ILU(0) preconditioner of A: psk_csr_ilu0, then the factors downloaded once, split into L (unit) and U and
+ * handed to the triangular-solve chain exactly as psk_prec_create_trisolve(n, L, l_unit = 1, U, u_unit = 0, no
+ * gathers) takes host factors (copied; the planner picks each factor's schedule). The result is a PSK_PREC_ILU:
+ * psk_prec_apply, psk_prec_info, psk_prec_trisolve_schedule and the solvers take it like any other. Errors as
+ * psk_csr_ilu0; A is not borrowed. Replaces nothing in the reference. */
+int psk_prec_create_ilu0(const psk_csr *A, psk_prec **out);
 
 /* ---- solvers ------------------------------------------------------------------------------ */
 /* M == NULL means identity. b, x: length n (local length for a distributed A); with loc ==

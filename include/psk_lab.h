@@ -105,6 +105,12 @@ int psk_lab_solver_layout(int32_t solver, int64_t n, int64_t ncols, int64_t maxi
 int psk_lab_gmres_internals(const psk_csr *A, int64_t maxiter, int32_t restart, int32_t gen, int32_t cols, double *Q,
                             double *H, double *R, double *CS, double *g, double *y, double *state);
 int psk_lab_gmres_prefill(psk_csr *A, int64_t maxiter, int32_t restart, int32_t gen, int32_t byte);
+/* Measurement (tools/ilu0_ab.py): where the last psk_csr_ilu0 / psk_prec_create_ilu0 of this process spent its time.
+ * out[0..6] = ms of the column sort and structure checks, of the pattern download and dependency levels, of the
+ * numeric launches (HIP events around them), of the value download and L / U split, of psk_prec_create_trisolve
+ * (planner and uploads; the last two are 0 after psk_csr_ilu0), then the level count and the lanes per row. Touches
+ * no GPU. */
+int psk_lab_ilu0_timing(double *out);
 #ifdef __cplusplus
 }
 #endif

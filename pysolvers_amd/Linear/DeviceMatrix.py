@@ -174,6 +174,17 @@ class DeviceCSR:
         N.check(N.lib.psk_csr_transpose(self._h, ctypes.byref(h)), "psk_csr_transpose")
         return DeviceCSR._adopt(h, self.n)
 
+    def ilu0(self):
+        """The ILU(0) factors of this matrix as one DeviceCSR F on its pattern, rows in ascending column order,
+        factored on the device (psk_csr_ilu0; the arithmetic is defined to the bit in include/psk.h):
+        L = strict-lower(F) with a unit diagonal, U = upper(F). Raises PskError with PSK_ERR_ARG for a missing
+        diagonal entry or a zero / non-finite pivot, PSK_ERR_UNSUPPORTED for a duplicate column in a row."""
+        if self.comm is not None:
+            raise ValueError("ILU(0) of a sharded matrix is not supported")
+        h = ctypes.c_void_p()
+        N.check(N.lib.psk_csr_ilu0(self._h, ctypes.byref(h)), "psk_csr_ilu0")
+        return DeviceCSR._adopt(h, self.ncols)
+
     def to_scipy(self):
         indptr = np.empty(self.n + 1, dtype=np.int32)
         indices = np.empty(self.nnz, dtype=np.int32)

@@ -8,6 +8,8 @@ from .Distributed import Communicator, fd_laplacian_2d_sharded, halo_cols, shard
 from .GMRESSolver import GMRES, GMRESSolver
 from .ILUTPreconditioner import (ILUTPreconditioner, LeftILUT, LeftILUTPreconditioner, RightILUT,
                                  RightILUTPreconditioner)
+from .ILU0Preconditioner import (ILU0Preconditioner, LeftILU0, LeftILU0Preconditioner, RightILU0,
+                                 RightILU0Preconditioner)
 from .ICPreconditioner import ICRightPreconditioner, RightIC
 from .IterativeLinearSolver import IterativeLinearSolver, IterativeLinearSolverType, mvmult
 from .LinearSolver import LinearSolver, LinearSolverType

@@ -95,6 +95,8 @@ SIGNATURES = {
     "psk_csr_matmat": (ctypes.c_int, [P, P, PP]),
     "psk_csr_transpose": (ctypes.c_int, [P, PP]),
     "psk_sa_prolongator": (ctypes.c_int, [P, P, I64, P, F64, I32, PP]),
+    "psk_csr_ilu0": (ctypes.c_int, [P, PP]),
+    "psk_prec_create_ilu0": (ctypes.c_int, [P, PP]),
     "psk_pcg": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_gmres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_bicgstab": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
@@ -138,6 +140,7 @@ LAB_SIGNATURES = {
                                             ctypes.POINTER(I32), ctypes.POINTER(I64)]),
     "psk_lab_gmres_internals": (ctypes.c_int, [P, I64, I32, I32, I32, P, P, P, P, P, P, P]),
     "psk_lab_gmres_prefill": (ctypes.c_int, [P, I64, I32, I32, I32]),
+    "psk_lab_ilu0_timing": (ctypes.c_int, [ctypes.POINTER(F64)]),
 }
 _lab = None
 

@@ -183,6 +183,14 @@ extern "C" int psk_lab_cheby_ab(const psk_prec *M, const double *v, int32_t reps
     return psk::cheby_ab(M, v, reps, fused_ms, pieces_ms);
 }
 
+extern "C" int psk_lab_ilu0_timing(double *out) {
+    if (!out) return psk::fail(PSK_ERR_ARG, "psk_lab_ilu0_timing: NULL argument");
+    const psk::Ilu0Timing &t = psk::ilu0_last_timing();
+    const double v[7] = {t.sort_ms, t.levels_ms, t.numeric_ms, t.split_ms, t.plan_ms, (double)t.levels, (double)t.width};
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
+    return PSK_OK;
+}
+
 extern "C" int psk_lab_amg_gs_pair(psk_prec *M, int32_t set, int32_t *levels_on, int32_t *levels_eligible) {
     using namespace psk;
     if (set < -1 || set > 1) return fail(PSK_ERR_ARG, "psk_lab_amg_gs_pair: set must be -1, 0 or 1");

@@ -979,6 +979,16 @@ int cheby_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);
 void cheby_free(Chebyshev *ch);
 // measurement: ms per step of `reps` back-to-back fused steps, and of the same step as four launches (cheby.hip)
 int cheby_ab(const psk_prec *M, const double *v, int reps, double *fused_ms, double *pieces_ms);
+// measurement (ilu0.hip; the lab library reads it): host wall time of the phases of the last psk_csr_ilu0 /
+// psk_prec_create_ilu0 — the column sort and structure checks, the pattern download and dependency levels, the
+// numeric launches (HIP events), then for the preconditioner the value download and L / U split and
+// psk_prec_create_trisolve (planner and uploads); the level count and the lanes per row
+struct Ilu0Timing {
+    double sort_ms = 0.0, levels_ms = 0.0, numeric_ms = 0.0, split_ms = 0.0, plan_ms = 0.0;
+    int64_t levels = 0;
+    int width = 0;
+};
+const Ilu0Timing &ilu0_last_timing();
 // preconditioners whose apply is not a single elementwise op (triangular solves, AMG, polynomials): the
 // Krylov drivers take their general path for these
 inline bool prec_is_general(const psk_prec *M) {

@@ -229,6 +229,10 @@ struct HostFactor {
 int split_factor(int64_t n, const int32_t *rp, const int32_t *ci, const double *va, bool lower, bool unit,
                  std::vector<int32_t> &orp, std::vector<int32_t> &oci, std::vector<double> &ova, std::vector<double> &dg);
 
+// Global dependency levels of F: lev[i] = the level of row i, order = the rows sorted by level (solve order inside
+// one), nlev = the number of levels.
+void level_order(const HostFactor &F, std::vector<int32_t> &order, std::vector<int32_t> &lev, int64_t &nlev);
+
 struct GridPlan {
     bool ok = false;
     int64_t w = 0, H = 0, sigma2 = 0, phase = 0, off = 0;   // g(y) = (sigma2 * y + phase) >> 1

@@ -79,7 +79,10 @@ constexpr double kLdsLevelUs = 0.15, kLdsBytesPerUs = 40e3;   // LDS schedule (p
 constexpr double kLevelStepUs = 0.30, kLevelBytesPerUs = 200e3;   // fitted: AMG level 1 of -FD 8192^2, 0.615 ms
 constexpr double kNarrowLevelUs = 0.8;    // narrow band local level (FD 8192^2 Gauss-Seidel: 12.6 ms / 16128 levels)
 
-// global dependency levels -> counting-sort the rows by level (stable: solve order inside a level)
+}  // namespace
+
+// global dependency levels -> counting-sort the rows by level (stable: solve order inside a level); shared with
+// the ILU(0) numeric phase (ilu0.hip), whose launches are the levels of strict-lower(A)
 void level_order(const HostFactor &F, std::vector<int32_t> &order, std::vector<int32_t> &lev, int64_t &nlev) {
     const int64_t n = F.n;
     lev.assign(n, 0);
@@ -101,6 +104,8 @@ void level_order(const HostFactor &F, std::vector<int32_t> &order, std::vector<i
         order[cnt[lev[i]]++] = (int32_t)i;
     }
 }
+
+namespace {
 
 // simulated time of the sync-free schedule: wave w processes order[w], order[w+W], ...
 double simulate_syncfree(const HostFactor &F, const std::vector<int32_t> &order, int64_t waves) {
