@@ -57,8 +57,7 @@ struct BicgState {
 // done = v != 0 and the stamp the host polls: k + 2 for a kernel of iteration k, 1 for the init
 __device__ __forceinline__ void bicg_set_done(BicgState *st, int32_t v, int64_t stamp) {
     st->done = v;
-    __hip_atomic_store(st->hdone, st->hgen | stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __threadfence_system();
+    done_stamp_store(st->hdone, st->hgen, stamp);
 }
 __device__ __forceinline__ void bicg_breakdown(BicgState *st, int32_t kind, int64_t k, int64_t nhist) {
     st->brk_kind = kind;

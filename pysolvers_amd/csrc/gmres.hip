@@ -2,7 +2,10 @@
 //
 // Krylov basis Q lives in HBM column-major (each q_j contiguous, n x (K+1)); the Hessenberg
 // column, the Givens table and g live in HBM too and are advanced by one lane of workgroup 0.
-// Per Arnoldi step k (one-shot launches, one 512-element tile per workgroup; no host sync):
+// Per Arnoldi step k (one-shot launches, one 512-element tile per workgroup). The host only enqueues: in front of
+// step k it waits for the event behind step k - 3 and reads the done stamp G3 stores when it raises `done`
+// (solve_loop.hpp StampPoll), so at most two steps are enqueued behind the one that ended the cycle, and they
+// return at once. It synchronises after the first cycle start (b = 0), at each cycle's end and for the results.
 //   G1      u = A M^-1 q_k, with q_0.u finished in-launch (gridsum)      (:107, first MGS dot)
 //   G2_j    h_jk (G1's or G2_{j-1}'s grid sum); u -= h_jk q_j; q_{j+1}.u (:110-112, MGS, j=0..k)
 //           finished in-launch (for j==k u.u, the norm)
@@ -34,6 +37,8 @@ struct GmresState {
     double tauNormB;
     double rec;      // last |g[k+1]|
     double true_resid;
+    int64_t *hdone;  // host-mapped done stamp (solve_loop.hpp): k + 2 for step k of a cycle, 1 for b = 0
+    int64_t hgen;    // this solve's generation in the stamp's high bits
 };
 
 __global__ __launch_bounds__(kBlock) void gm_selfdot_kernel(int64_t n, const double *__restrict__ v,
@@ -52,7 +57,8 @@ __global__ __launch_bounds__(kBlock) void gm_selfdot_kernel(int64_t n, const dou
 __global__ __launch_bounds__(kBlock) void gm_start_kernel(int64_t n, const double *__restrict__ r0,
                                                           double *__restrict__ q0, const double *__restrict__ part,
                                                           int np, double *__restrict__ g, int Kp1, GmresState *st,
-                                                          double tau, int first, double normb_caller) {
+                                                          double tau, int first, double normb_caller,
+                                                          int64_t *hdone, int64_t hgen) {
     __shared__ double sh[kWaves];
     const double bb = reduce_partials(part, np, 1, sh);
     const double beta = sqrt(bb);
@@ -63,7 +69,12 @@ __global__ __launch_bounds__(kBlock) void gm_start_kernel(int64_t n, const doubl
             st->normB = nb;
             st->tauNormB = tau * nb;
             st->zero_b = beta == 0.0;
-            if (beta == 0.0) st->done = 1;     // :67-68
+            st->hdone = hdone;
+            st->hgen = hgen;
+            if (beta == 0.0) {                 // :67-68
+                st->done = 1;
+                done_stamp_store(hdone, hgen, 1);
+            }
         }
         for (int j = 0; j < Kp1; ++j) g[j] = beta * (j == 0 ? 1.0 : 0.0);   // g = beta*e1
     }
@@ -163,6 +174,7 @@ __global__ __launch_bounds__(kBlock) void gm_normalize_kernel(
             st->brk = brk;
             st->kconv = k;
             st->done = 1;
+            done_stamp_store(st->hdone, st->hgen, k + 2);
         }
     }
 }
@@ -240,11 +252,15 @@ struct GmresWork {
     double *Q, *u, *x, *bv, *w, *tt;   // w, tt: general (ILU) preconditioner only (M^-1 q_k, scratch)
     GmresState *st;
     double *H, *R, *CS, *g, *pa, *dhist, *dy, *hv;
+    int64_t ldq;     // doubles between two columns of Q (a column is padded to 256 bytes)
+    size_t hbytes;   // the extent of H, and of R
 };
 // the layout of A->ws (big) and A->ws_small (sm): run on null-based carvers for the sizes, then on the buffers
 static void gm_layout(Carve &big, Carve &sm, int64_t n, int64_t maxiter, int64_t K, bool gen, GmresWork &w) {
     const size_t vec = (size_t)n * 8, ld = (size_t)K + 1;
-    w.Q = big.take<double>(((vec + 255) / 256 * 256) * ld);
+    const size_t col = (vec + 255) / 256 * 256;
+    w.ldq = (int64_t)(col / 8);
+    w.Q = big.take<double>(col * ld);
     w.u = big.take<double>(vec);
     w.x = big.take<double>(vec);
     w.bv = big.take<double>(vec);
@@ -252,7 +268,9 @@ static void gm_layout(Carve &big, Carve &sm, int64_t n, int64_t maxiter, int64_t
     w.tt = gen ? big.take<double>(vec) : nullptr;
     w.st = sm.take<GmresState>(sizeof(GmresState));
     w.H = sm.take<double>(ld * K * 8);
+    const size_t hend = sm.off;
     w.R = sm.take<double>(ld * K * 8);
+    w.hbytes = sm.off - hend;
     w.CS = sm.take<double>((size_t)2 * K * 8);
     w.g = sm.take<double>(ld * 8);
     w.pa = sm.take<double>((size_t)kMaxGrid * 8);   // partials of the cycle-start norm / the residual's sum
@@ -268,12 +286,9 @@ void gmres_layout_probe(int64_t n, int64_t maxiter, int64_t restart, bool gen, s
     bytes[0] = (int64_t)big.off;
     bytes[1] = (int64_t)sm.off;
 }
-// the regions psk_gmres(maxiter, restart, gen) carved on this matrix: the same gm_layout over A->ws / A->ws_small.
-// grow: size the two buffers as the solve would (a later solve then keeps them); otherwise PSK_ERR_ARG when either
-// is smaller than that layout. Host code only (psk_lab_gmres_internals, psk_lab_gmres_prefill).
-int gmres_work_view(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool grow, GmresView *v) {
-    if (!A || !v || maxiter < 0 || restart < 0 || A->n < 0) return fail(PSK_ERR_ARG, "gmres_work_view: bad arguments");
-    int64_t need[2];
+// A->ws and A->ws_small carved by gm_layout; need[2]: the bytes of each the layout covers. grow: size the two
+// buffers first (a later solve then keeps them); otherwise PSK_ERR_ARG when either is smaller than the layout.
+static int gm_workspace(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool grow, GmresWork &w, int64_t *need) {
     gmres_layout_probe(A->n, maxiter, restart, gen, nullptr, need);
     if (grow) {
         PSK_TRY(A->ws.ensure((size_t)need[0]));
@@ -282,12 +297,19 @@ int gmres_work_view(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool
     if (!A->ws.p || !A->ws_small.p || A->ws.bytes < (size_t)need[0] || A->ws_small.bytes < (size_t)need[1])
         return fail(PSK_ERR_ARG, "gmres_work_view: the matrix's workspace is smaller than this layout");
     Carve big{A->ws.as<char>()}, sm{A->ws_small.as<char>()};
+    gm_layout(big, sm, A->n, maxiter, gm_basis(maxiter, restart), gen, w);
+    return PSK_OK;
+}
+// the regions psk_gmres(maxiter, restart, gen) carved on this matrix. Host code only (psk_lab_gmres_internals,
+// psk_lab_gmres_prefill).
+int gmres_work_view(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool grow, GmresView *v) {
+    if (!A || !v || maxiter < 0 || restart < 0 || A->n < 0) return fail(PSK_ERR_ARG, "gmres_work_view: bad arguments");
+    int64_t need[2];
     GmresWork w;
-    const int64_t K = gm_basis(maxiter, restart);
-    gm_layout(big, sm, A->n, maxiter, K, gen, w);
+    PSK_TRY(gm_workspace(A, maxiter, restart, gen, grow, w, need));
     v->n = A->n;
-    v->K = K;
-    v->ldq = (int64_t)((((size_t)A->n * 8 + 255) / 256 * 256) / 8);
+    v->K = gm_basis(maxiter, restart);
+    v->ldq = w.ldq;
     v->Q = w.Q;
     v->H = w.H;
     v->R = w.R;
@@ -307,6 +329,242 @@ int gmres_work_view(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool
     return PSK_OK;
 }
 
+struct GmresRun {
+    psk_csr *A;
+    const psk_prec *M;
+    const psk_ctl *ctl;
+    Context *c;
+    hipStream_t s;
+    int64_t n, nv, K;        // nv: the one-shot grid of the MGS kernels; K: the basis of a full cycle
+    int gv, ld;              // gv: the grid of the cycle start; ld = K + 1, the leading dimension of H and R
+    bool gen;                // general (ILU) preconditioner: M^-1 q_k is materialised in w before the SpMV
+    const double *dinv;
+    GmresWork w;
+    SolveKit *kit;
+    int64_t it, spmvs;       // iterations completed before this cycle; SpMV launches enqueued
+    bool hit_maxiter;
+    GmresState hs;           // the device state as last read (gm_read_state)
+};
+
+// before anything is allocated: the K + 1 basis columns and four more vectors, as the layout pads them, against
+// the free HBM
+static int gm_fits_hbm(const GmresRun &r) {
+    Carve big, sm;
+    GmresWork w;
+    gm_layout(big, sm, r.n, r.ctl->maxiter, r.K, r.gen, w);
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess && (size_t)(r.K + 5) * w.ldq * 8 > fr)
+        return fail(PSK_ERR_ALLOC, "psk_gmres: Krylov basis of " + std::to_string(r.K + 1) +
+                                       " vectors does not fit in HBM; use restart");
+    return PSK_OK;
+}
+
+static int gm_read_state(GmresRun &r) {
+    PSK_HIP(hipMemcpyAsync(&r.hs, r.w.st, sizeof(r.hs), hipMemcpyDeviceToHost, r.s));
+    PSK_HIP(hipStreamSynchronize(r.s));
+    return PSK_OK;
+}
+
+// cycle start: r0 = b (first cycle, :87) or b - A x (restart); beta = ||r0||, q_0, g
+static int gm_cycle_start(GmresRun &r, const StampPoll &poll, bool first) {
+    GmresWork &w = r.w;
+    const double *r0 = w.bv;
+    int np = r.gv;   // partials of ||r0||^2: gm_selfdot_kernel's, one per workgroup
+    if (first) {
+        hipLaunchKernelGGL(gm_selfdot_kernel, dim3(r.gv), dim3(kBlock), 0, r.s, r.n, w.bv, w.pa);
+    } else {
+        PSK_TRY(launch_spmv(r.A, kSpmvResid, w.x, w.u, nullptr, w.bv, w.pa, nullptr, r.s));
+        ++r.spmvs;
+        r0 = w.u;
+        np = 1;      // the residual SpMV finishes its sum in-launch (gridsum)
+    }
+    hipLaunchKernelGGL(gm_start_kernel, dim3(r.gv), dim3(kBlock), 0, r.s, r.n, r0, w.Q, w.pa, np, w.g, r.ld, w.st,
+                       r.ctl->tau, first ? 1 : 0, first ? r.ctl->norm_b : 0.0, poll.hdone(), poll.hgen());
+    PSK_HIP(hipGetLastError());
+    return PSK_OK;
+}
+
+// Arnoldi step k of the cycle: [w = M^-1 q_k], u = A M^-1 q_k with q_0.u, the k + 1 MGS launches, the normalisation
+static int gm_step(GmresRun &r, int64_t k) {
+    GmresWork &w = r.w;
+    hipStream_t s = r.s;
+    const int64_t n = r.n;
+    const dim3 g((unsigned)r.nv), blk(kBlock);
+    const double *qk = w.Q + k * w.ldq;
+    if (r.gen) {   // u = A (M^-1 q_k): materialise M^-1 q_k (GMRESSolver.py:107)
+        PSK_TRY(prec_apply_dev(r.M, n, qk, w.w, s));
+        PSK_TRY(launch_spmv(r.A, kSpmvPlainDot, w.w, w.u, nullptr, w.Q, w.hv, &w.st->done, s));
+    } else {
+        PSK_TRY(launch_spmv(r.A, r.dinv ? kSpmvJacobiDot : kSpmvPlainDot, qk, w.u, r.dinv, w.Q, w.hv, &w.st->done, s));
+    }
+    ++r.spmvs;
+    // hv[0] = q_0.u (the SpMV's grid sum), hv[j+1] = the dot MGS step j finishes
+    double *hcol = w.H + k * r.ld;
+    for (int64_t j = 0; j <= k; ++j) {
+        const double *qj = w.Q + j * w.ldq;
+        const double *qn = j < k ? qj + w.ldq : nullptr;
+        GridSum gsj;
+        PSK_TRY(gridsum_prepare(r.c, r.nv, 1, w.hv + j + 1, &gsj));
+        hipLaunchKernelGGL(gm_mgs_kernel, g, blk, 0, s, n, w.u, qj, qn, w.hv + j, hcol, (int)j, gsj, w.st);
+    }
+    hipLaunchKernelGGL(gm_normalize_kernel, g, blk, 0, s, n, w.u, w.Q + (k + 1) * w.ldq, w.hv + k + 1, w.H, w.R, w.CS,
+                       w.g, r.ld, (int)k, r.it + k, w.st, w.dhist);
+    PSK_HIP(hipGetLastError());
+    return PSK_OK;
+}
+
+// y = solve(R[:kc+1,:kc+1], g[:kc+1]) on the host; x (+)= M^-1 (Q[:, :kc+1] y)   (:159-160)
+static int gm_update_x(GmresRun &r, int kc, bool accumulate) {
+    GmresWork &w = r.w;
+    hipStream_t s = r.s;
+    const int64_t n = r.n;
+    std::vector<double> hR((size_t)r.ld * r.K), hg((size_t)r.ld), y;
+    PSK_HIP(hipMemcpyAsync(hR.data(), w.R, hR.size() * 8, hipMemcpyDeviceToHost, s));
+    PSK_HIP(hipMemcpyAsync(hg.data(), w.g, hg.size() * 8, hipMemcpyDeviceToHost, s));
+    PSK_HIP(hipStreamSynchronize(s));
+    if (!small_solve(kc + 1, hR.data(), r.ld, hg.data(), y))
+        return fail(PSK_ERR_ARG, "GMRES least-squares system is singular (LinAlgError in the reference)");
+    PSK_HIP(hipMemcpyAsync(w.dy, y.data(), (size_t)(kc + 1) * 8, hipMemcpyHostToDevice, s));
+    const dim3 g((unsigned)((n + kBlock - 1) / kBlock)), blk(kBlock);
+    const int acc = accumulate ? 1 : 0;
+    if (!r.gen) {
+        hipLaunchKernelGGL(gm_update_x_kernel, g, blk, 0, s, n, w.Q, w.ldq, w.dy, kc + 1, r.dinv, w.x, acc);
+    } else {   // the gemv into w, the preconditioner into tt, then add / copy
+        hipLaunchKernelGGL(gm_update_x_kernel, g, blk, 0, s, n, w.Q, w.ldq, w.dy, kc + 1, (const double *)nullptr, w.w, 0);
+        PSK_HIP(hipGetLastError());
+        PSK_TRY(prec_apply_dev(r.M, n, w.w, w.tt, s));
+        hipLaunchKernelGGL(gm_add_or_copy_kernel, g, blk, 0, s, n, w.tt, w.x, acc);
+    }
+    PSK_HIP(hipGetLastError());
+    return PSK_OK;
+}
+
+// the cycle raised `done` at its step hs.kconv: x, the true residual ||b - A x|| and the result  (:159-174)
+static int gm_converged(GmresRun &r, psk_result *res) {
+    GmresWork &w = r.w;
+    const int kc = r.hs.kconv;
+    PSK_TRY(gm_update_x(r, kc, r.it > 0));
+    PSK_TRY(launch_spmv(r.A, kSpmvResid, w.x, w.u, nullptr, w.bv, w.pa, nullptr, r.s));
+    ++r.spmvs;
+    hipLaunchKernelGGL(gm_true_resid_kernel, dim3(1), dim3(kBlock), 0, r.s, w.pa, 1, w.st);
+    PSK_HIP(hipGetLastError());
+    PSK_TRY(gm_read_state(r));
+    const GmresState &hs = r.hs;
+    res->iters = r.it + kc + 1;
+    res->exit = hs.brk ? PSK_EXIT_ARNOLDI_BREAKDOWN : PSK_EXIT_TOLERANCE;
+    res->resid = hs.true_resid;
+    res->resid_recursive = hs.rec;
+    if (hs.true_resid <= hs.tauNormB) {
+        res->status = PSK_CONVERGED;
+        res->success = 1;
+    } else {
+        res->status = PSK_TRUE_RESID_FAIL;
+        res->success = 0;
+        std::snprintf(res->msg, sizeof(res->msg),
+                      "GMRES failure: true residual %12.5g did not meet tolerance tau=%12.5g. "
+                      "Recursive residual was %12.5g.",
+                      hs.true_resid, r.ctl->tau, hs.rec);
+    }
+    return PSK_OK;
+}
+
+// a cycle of Kc steps ended without `done`: x from all of them, and the result when that was maxiter (hit_maxiter)
+static int gm_cycle_end(GmresRun &r, int64_t Kc, psk_result *res) {
+    PSK_TRY(gm_update_x(r, (int)Kc - 1, r.it > 0));
+    r.it += Kc;
+    if (r.it < r.ctl->maxiter) return PSK_OK;
+    // maxiter reached (reference: NameError at :180) -> handleMaxiter(k, x, |g|, ...)
+    r.hit_maxiter = true;
+    res->exit = PSK_EXIT_MAXITER;
+    res->iters = r.ctl->maxiter > 0 ? r.ctl->maxiter - 1 : 0;
+    res->resid = r.hs.rec;
+    res->resid_recursive = r.hs.rec;
+    if (r.ctl->fail_on_maxiter) {
+        res->status = PSK_MAXITER;
+        res->success = 0;
+        std::snprintf(res->msg, sizeof(res->msg), "failure to converge");
+    } else {
+        res->status = PSK_CONVERGED;
+        res->success = 1;
+    }
+    return PSK_OK;
+}
+
+// behind the last cycle: the checks of the in-launch reductions, loop_ms, norm_b, the b = 0 result, the history, x
+static int gm_report(GmresRun &r, psk_result *res, double *hist, double *xout, int32_t loc) {
+    const GmresState &hs = r.hs;
+    const int64_t maxiter = r.ctl->maxiter;
+    PSK_HIP(hipEventRecord(r.kit->ev1, r.s));
+    PSK_HIP(hipStreamSynchronize(r.s));
+    // an expired in-launch reduction wait (MGS / normalisation / SpMV dots) poisons h with NaN; report it
+    // as the error it is rather than as a numerical non-convergence (and never to a later solve)
+    PSK_TRY(gridsum_check(r.c));
+    if (r.gen) PSK_TRY(prec_check_error(r.M, r.s));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, r.kit->ev0, r.kit->ev1);
+    res->loop_ms = ms;
+    res->norm_b = hs.normB;
+    res->spmv_launches = r.spmvs;
+    if (hs.zero_b) {   // b = 0: handleConvergence(0, zeros, 0, 0)
+        res->status = PSK_CONVERGED;
+        res->success = 1;
+        res->iters = 1;
+        res->resid = 0.0;
+        res->exit = PSK_EXIT_NONE;
+    }
+    // every step reported one residual (reportIter, :155): iters + 1 entries at maxiter (k = maxiter - 1)
+    const int64_t nh = res->iters + (r.hit_maxiter ? 1 : 0);
+    const int64_t nhc = hs.zero_b ? 0 : (nh < maxiter ? nh : maxiter);
+    res->hist_len = nhc;
+    if (hist && nhc > 0) PSK_HIP(hipMemcpy(hist, r.w.dhist, (size_t)nhc * 8, hipMemcpyDeviceToHost));
+    PSK_TRY(from_device_vec(r.w.x, loc, r.n, xout, r.s));
+    PSK_HIP(hipStreamSynchronize(r.s));
+    return PSK_OK;
+}
+
+static int gm_solve(GmresRun &r, const double *b, double *xout, psk_result *res, double *hist, int32_t loc) {
+    hipStream_t s = r.s;
+    const int64_t maxiter = r.ctl->maxiter;
+    int64_t need[2];
+    PSK_TRY(gm_workspace(r.A, maxiter, r.ctl->restart, r.gen, true, r.w, need));
+    GmresWork &w = r.w;
+    PSK_TRY(solve_kit(r.c, false, &r.kit));
+    StampPoll poll(r.kit);   // the host-mapped done stamp gm_start_kernel and gm_normalize_kernel write
+    PSK_HIP(hipMemsetAsync(w.st, 0, sizeof(GmresState), s));
+    // Hessenberg and rotated copies start at zero: entries below the subdiagonal are never written
+    // and the least-squares solve reads them (HBar = np.zeros, GMRESSolver.py:80)
+    PSK_HIP(hipMemsetAsync(w.H, 0, w.hbytes, s));
+    PSK_HIP(hipMemsetAsync(w.R, 0, w.hbytes, s));
+    PSK_TRY(to_device_vec(b, loc, r.n, w.bv, s));
+    PSK_HIP(hipMemsetAsync(w.x, 0, (size_t)r.n * 8, s));
+    PSK_HIP(hipEventRecord(r.kit->ev0, s));
+    for (bool first = true;; first = false) {
+        PSK_TRY(gm_cycle_start(r, poll, first));
+        if (first) {   // the one wait in front of the loop: b = 0 runs no step (:67-68)
+            PSK_TRY(gm_read_state(r));
+            if (r.hs.zero_b) break;
+        }
+        const int64_t Kc = maxiter - r.it < r.K ? maxiter - r.it : r.K;
+        // Step numbers and stamps count from the cycle's start. A stamp ends the solve, so none is left over from an
+        // earlier cycle, and the stream is drained between cycles: step k is not enqueued iff `done` was raised at
+        // a step <= k - 3 of this cycle.
+        for (int64_t k = 0; k < Kc; ++k) {
+            bool stop;
+            PSK_TRY(poll.step<2>(k, 1, s, &stop));
+            if (stop) break;
+            PSK_TRY(gm_step(r, k));
+        }
+        PSK_TRY(gm_read_state(r));
+        if (r.hs.done) {
+            PSK_TRY(gm_converged(r, res));
+            break;
+        }
+        PSK_TRY(gm_cycle_end(r, Kc, res));
+        if (r.hit_maxiter) break;
+    }
+    return gm_report(r, res, hist, xout, loc);
+}
+
 }  // namespace psk
 
 using namespace psk;
@@ -317,239 +575,34 @@ extern "C" int psk_gmres(const psk_csr *Ac, const psk_prec *M, const double *b, 
     if (ctl->maxiter < 0 || ctl->restart < 0) return fail(PSK_ERR_ARG, "psk_gmres: negative maxiter/restart");
     if (M && M->n != Ac->n) return fail(PSK_ERR_ARG, "psk_gmres: preconditioner size mismatch");
     if (!Ac->comm && Ac->ncols != Ac->n) return fail(PSK_ERR_ARG, "psk_gmres: matrix must be square");
-    psk_csr *A = const_cast<psk_csr *>(Ac);
-    if (A->comm && A->comm->nranks > 1)
+    if (Ac->comm && Ac->comm->nranks > 1)
         return fail(PSK_ERR_UNSUPPORTED, "psk_gmres: sharded GMRES not built (replicas only)");
-    Context *c;
-    PSK_TRY(ctx(&c));
-    std::lock_guard<std::mutex> solve_lock(c->solve_mu);
-    hipStream_t s = c->stream;
+    GmresRun r{};
+    r.A = const_cast<psk_csr *>(Ac);
+    r.M = M;
+    r.ctl = ctl;
+    PSK_TRY(ctx(&r.c));
+    std::lock_guard<std::mutex> solve_lock(r.c->solve_mu);
+    r.s = r.c->stream;
     std::memset(res, 0, sizeof(*res));
-    const int64_t n = A->n, maxiter = ctl->maxiter;
-    const int64_t K = gm_basis(maxiter, ctl->restart);
-    const int ld = (int)(K + 1);
-    const double *dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
-    const int gs = 1;   // partials of a dot-mode SpMV: it finishes its sum in-launch (gridsum)
-    const int gv = grid_for_rows(c, n, kVecTile);
-    const int64_t nv = n > 0 ? (n + kVecTile - 1) / kVecTile : 1;   // one-shot grid of the MGS kernels
-    if (nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_gmres: vector too long for a one-shot grid");
-    const size_t vec = ((size_t)n * 8 + 255) / 256 * 256;
-    const size_t qbytes = vec * (size_t)(K + 1);
-    {
-        size_t fr = 0, tot = 0;
-        if (hipMemGetInfo(&fr, &tot) == hipSuccess && qbytes + 4 * vec > fr)
-            return fail(PSK_ERR_ALLOC, "psk_gmres: Krylov basis of " + std::to_string(K + 1) +
-                                           " vectors does not fit in HBM; use restart");
-    }
-    // general (ILU) preconditioner: M^-1 q_k is materialised in w before the SpMV; t is scratch
-    const bool gen = prec_is_general(M);
-    int64_t need[2];
-    gmres_layout_probe(n, maxiter, ctl->restart, gen, nullptr, need);
-    PSK_TRY(A->ws.ensure((size_t)need[0]));
-    PSK_TRY(A->ws_small.ensure((size_t)need[1]));
-    Carve big{A->ws.as<char>()}, sm{A->ws_small.as<char>()};
-    GmresWork gw;
-    gm_layout(big, sm, n, maxiter, K, gen, gw);
-    double *Q = gw.Q, *u = gw.u, *x = gw.x, *bv = gw.bv, *w = gw.w, *tt = gw.tt, *H = gw.H, *R = gw.R, *CS = gw.CS,
-           *g = gw.g, *pa = gw.pa, *dhist = gw.dhist, *dy = gw.dy, *hv = gw.hv;
-    GmresState *st = gw.st;
-    const size_t hb = ((size_t)ld * K * 8 + 255) / 256 * 256;
-
-    // events and the poll words come from the device's SolveKit (allocated once, round 4)
-    SolveKit *kit;
-    PSK_TRY(solve_kit(c, false, &kit));
-    hipEvent_t ev0 = kit->ev0, ev1 = kit->ev1;
-    PSK_HIP(hipMemsetAsync(st, 0, sizeof(GmresState), s));
-    // Hessenberg and rotated copies start at zero: entries below the subdiagonal are never written
-    // and the least-squares solve reads them (HBar = np.zeros, GMRESSolver.py:80)
-    PSK_HIP(hipMemsetAsync(H, 0, hb, s));
-    PSK_HIP(hipMemsetAsync(R, 0, hb, s));
-    PSK_TRY(to_device_vec(b, loc, n, bv, s));
-    PSK_HIP(hipMemsetAsync(x, 0, (size_t)n * 8, s));
-    PSK_HIP(hipEventRecord(ev0, s));
-
-    const int L = 2, NS = kPollSlots;
-    static_assert(kPollSlots >= L + 2, "poll slots");
-    int32_t *hflag = reinterpret_cast<int32_t *>(static_cast<char *>(kit->hstage) + 1024);   // pinned, NS words
-    hipEvent_t *fev = kit->fev;
-
-    int rc = PSK_OK;
-    int64_t it = 0;          // global iterations completed before this cycle
-    bool first = true, finished = false, hit_maxiter = false;
-    GmresState hs{};
-    std::vector<double> hR, hg, y;
-    int64_t spmv_count = 0;
-
-    auto run_finalize = [&](int kc, bool accumulate) -> int {
-        // y = solve(R[:kc+1,:kc+1], g[:kc+1]); x (+)= M^-1 Q y
-        hR.resize((size_t)ld * K);
-        hg.resize((size_t)ld);
-        PSK_HIP(hipMemcpyAsync(hR.data(), R, (size_t)ld * K * 8, hipMemcpyDeviceToHost, s));
-        PSK_HIP(hipMemcpyAsync(hg.data(), g, (size_t)ld * 8, hipMemcpyDeviceToHost, s));
-        PSK_HIP(hipStreamSynchronize(s));
-        if (!small_solve(kc + 1, hR.data(), ld, hg.data(), y))
-            return fail(PSK_ERR_ARG, "GMRES least-squares system is singular (LinAlgError in the reference)");
-        PSK_HIP(hipMemcpyAsync(dy, y.data(), (size_t)(kc + 1) * 8, hipMemcpyHostToDevice, s));
-        const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
-        if (!gen) {
-            hipLaunchKernelGGL(gm_update_x_kernel, dim3(nb), dim3(kBlock), 0, s, n, Q, (int64_t)(vec / 8), dy,
-                               kc + 1, dinv, x, accumulate ? 1 : 0);
-            PSK_HIP(hipGetLastError());
-            return PSK_OK;
-        }
-        // x (+)= M^-1 (Q y): gemv into w, apply the preconditioner into tt, then add/copy
-        hipLaunchKernelGGL(gm_update_x_kernel, dim3(nb), dim3(kBlock), 0, s, n, Q, (int64_t)(vec / 8), dy, kc + 1,
-                           (const double *)nullptr, w, 0);
-        PSK_HIP(hipGetLastError());
-        PSK_TRY(prec_apply_dev(M, n, w, tt, s));
-        hipLaunchKernelGGL(gm_add_or_copy_kernel, dim3(nb), dim3(kBlock), 0, s, n, tt, x, accumulate ? 1 : 0);
-        PSK_HIP(hipGetLastError());
+    r.n = Ac->n;
+    r.K = gm_basis(ctl->maxiter, ctl->restart);
+    r.ld = (int)(r.K + 1);
+    r.gv = grid_for_rows(r.c, r.n, kVecTile);
+    r.nv = r.n > 0 ? (r.n + kVecTile - 1) / kVecTile : 1;
+    if (r.nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_gmres: vector too long for a one-shot grid");
+    r.gen = prec_is_general(M);
+    r.dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
+    PSK_TRY(gm_fits_hbm(r));
+    if (r.n == 0) {   // no rows: b = 0
+        res->status = PSK_CONVERGED;
+        res->success = 1;
+        res->iters = 1;
+        res->exit = PSK_EXIT_NONE;
         return PSK_OK;
-    };
-
-    while (rc == PSK_OK && !finished) {
-        // ---- cycle start: r0 = b (first cycle, :87) or b - A x (restart)
-        if (first) {
-            hipLaunchKernelGGL(gm_selfdot_kernel, dim3(gv), dim3(kBlock), 0, s, n, bv, pa);
-            hipLaunchKernelGGL(gm_start_kernel, dim3(gv), dim3(kBlock), 0, s, n, bv, Q, pa, gv, g, ld, st,
-                               ctl->tau, 1, ctl->norm_b);
-        } else {
-            if ((rc = launch_spmv(A, kSpmvResid, x, u, nullptr, bv, pa, nullptr, s)) != PSK_OK) break;
-            ++spmv_count;
-            hipLaunchKernelGGL(gm_start_kernel, dim3(gv), dim3(kBlock), 0, s, n, u, Q, pa, gs, g, ld, st,
-                               ctl->tau, 0, 0.0);
-        }
-        if (hipGetLastError() != hipSuccess) { rc = fail(PSK_ERR_HIP, "gmres start"); break; }
-        if (first && n > 0) {
-            if (hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess) { rc = fail(PSK_ERR_HIP, "gmres state"); break; }
-            if (hs.zero_b) {   // b = 0: handleConvergence(0, zeros, 0, 0)
-                finished = true;
-                break;
-            }
-        }
-        if (n == 0) {
-            hs.zero_b = 1;
-            finished = true;
-            break;
-        }
-        first = false;
-        const int64_t Kc = (maxiter - it) < K ? (maxiter - it) : K;
-        int64_t k = 0;
-        for (; k < Kc; ++k) {
-            if (k > 0) {   // poll with a lag of L steps
-                const int slot = (int)((k - 1) % NS);
-                if (hipMemcpyAsync(&hflag[slot], &st->done, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                    hipEventRecord(fev[slot], s) != hipSuccess) { rc = fail(PSK_ERR_HIP, "poll"); break; }
-                if (k - 1 - L >= 0) {
-                    const int os = (int)((k - 1 - L) % NS);
-                    if (hipEventSynchronize(fev[os]) != hipSuccess) { rc = fail(PSK_ERR_HIP, "poll sync"); break; }
-                    if (hflag[os]) break;
-                }
-            }
-            const double *qk = Q + (size_t)k * (vec / 8);
-            const double *q0 = Q;
-            if (gen) {   // u = A (M^-1 q_k): materialise M^-1 q_k (GMRESSolver.py:107)
-                if ((rc = prec_apply_dev(M, n, qk, w, s)) != PSK_OK) break;
-                if ((rc = launch_spmv(A, kSpmvPlainDot, w, u, nullptr, q0, hv, &st->done, s)) != PSK_OK) break;
-            } else if ((rc = launch_spmv(A, dinv ? kSpmvJacobiDot : kSpmvPlainDot, qk, u, dinv, q0, hv, &st->done,
-                                         s)) != PSK_OK)
-                break;
-            ++spmv_count;
-            // hv[0] = q_0.u (the SpMV's grid sum), hv[j+1] = the dot MGS step j finishes
-            double *hcol = H + (size_t)k * ld;
-            for (int64_t j = 0; j <= k; ++j) {
-                const double *qj = Q + (size_t)j * (vec / 8);
-                const double *qn = j < k ? Q + (size_t)(j + 1) * (vec / 8) : nullptr;
-                GridSum gsj;
-                if ((rc = gridsum_prepare(c, nv, 1, hv + j + 1, &gsj)) != PSK_OK) break;
-                hipLaunchKernelGGL(gm_mgs_kernel, dim3((unsigned)nv), dim3(kBlock), 0, s, n, u, qj, qn, hv + j, hcol,
-                                   (int)j, gsj, st);
-            }
-            if (rc != PSK_OK) break;
-            hipLaunchKernelGGL(gm_normalize_kernel, dim3((unsigned)nv), dim3(kBlock), 0, s, n, u,
-                               Q + (size_t)(k + 1) * (vec / 8), hv + k + 1, H, R, CS, g, ld, (int)k, it + k, st,
-                               dhist);
-            if (hipGetLastError() != hipSuccess) { rc = fail(PSK_ERR_HIP, "gmres step launch"); break; }
-        }
-        if (rc != PSK_OK) break;
-        if (hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { rc = fail(PSK_ERR_HIP, "gmres state"); break; }
-        if (hs.done) {
-            // converged at step kc: x = M^-1 Q y, true residual (:159-174)
-            const int kc = hs.kconv;
-            if ((rc = run_finalize(kc, it > 0)) != PSK_OK) break;
-            if ((rc = launch_spmv(A, kSpmvResid, x, u, nullptr, bv, pa, nullptr, s)) != PSK_OK) break;
-            ++spmv_count;
-            hipLaunchKernelGGL(gm_true_resid_kernel, dim3(1), dim3(kBlock), 0, s, pa, gs, st);
-            if (hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess) { rc = fail(PSK_ERR_HIP, "gmres state"); break; }
-            res->iters = it + kc + 1;
-            res->exit = hs.brk ? PSK_EXIT_ARNOLDI_BREAKDOWN : PSK_EXIT_TOLERANCE;
-            res->resid = hs.true_resid;
-            res->resid_recursive = hs.rec;
-            if (hs.true_resid <= hs.tauNormB) {
-                res->status = PSK_CONVERGED;
-                res->success = 1;
-            } else {
-                res->status = PSK_TRUE_RESID_FAIL;
-                res->success = 0;
-                std::snprintf(res->msg, sizeof(res->msg),
-                              "GMRES failure: true residual %12.5g did not meet tolerance tau=%12.5g. "
-                              "Recursive residual was %12.5g.",
-                              hs.true_resid, ctl->tau, hs.rec);
-            }
-            finished = true;
-        } else {
-            it += Kc;
-            if ((rc = run_finalize((int)Kc - 1, it - Kc > 0)) != PSK_OK) break;
-            if (it >= maxiter) {
-                // maxiter reached (reference: NameError at :180) -> handleMaxiter(k, x, |g|, ...)
-                hit_maxiter = true;
-                res->exit = PSK_EXIT_MAXITER;
-                res->iters = maxiter > 0 ? maxiter - 1 : 0;
-                res->resid = hs.rec;
-                res->resid_recursive = hs.rec;
-                if (ctl->fail_on_maxiter) {
-                    res->status = PSK_MAXITER;
-                    res->success = 0;
-                    std::snprintf(res->msg, sizeof(res->msg), "failure to converge");
-                } else {
-                    res->status = PSK_CONVERGED;
-                    res->success = 1;
-                }
-                finished = true;
-            }
-        }
     }
-    if (rc == PSK_OK && hipEventRecord(ev1, s) != hipSuccess) rc = fail(PSK_ERR_HIP, "event");
-    if (rc == PSK_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(PSK_ERR_HIP, "gmres sync");
-    // an expired in-launch reduction wait (MGS / normalisation / SpMV dots) poisons h with NaN; report it
-    // as the error it is rather than as a numerical non-convergence (and never to a later solve)
-    if (rc == PSK_OK) rc = gridsum_check(c);
-    if (rc == PSK_OK && gen) rc = prec_check_error(M, s);
-    if (rc == PSK_OK) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ev0, ev1);
-        res->loop_ms = ms;
-        res->norm_b = hs.normB;
-        res->spmv_launches = spmv_count;
-        if (hs.zero_b) {
-            res->status = PSK_CONVERGED;
-            res->success = 1;
-            res->iters = 1;
-            res->resid = 0.0;
-            res->exit = PSK_EXIT_NONE;
-        }
-        // every step reported one residual (reportIter, :155): iters + 1 entries at maxiter (k = maxiter - 1)
-        const int64_t nh = res->iters + (hit_maxiter ? 1 : 0);
-        const int64_t nhc = hs.zero_b ? 0 : (nh < maxiter ? nh : maxiter);
-        res->hist_len = nhc;
-        if (hist && nhc > 0 &&
-            hipMemcpy(hist, dhist, (size_t)nhc * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(PSK_ERR_HIP, "hist copy");
-        if (rc == PSK_OK) rc = from_device_vec(x, loc, n, xout, s);
-        if (rc == PSK_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(PSK_ERR_HIP, "x copy");
-    }
+    const int rc = gm_solve(r, b, xout, res, hist, loc);
+    // a solve that failed on the host side leaves no kernel of its own running behind the next solve
+    if (rc != PSK_OK) (void)hipStreamSynchronize(r.s);
     return rc;
 }

@@ -26,10 +26,7 @@ struct PcgState {
 // iteration k, 1 for the init
 __device__ __forceinline__ void set_done(PcgState *st, int32_t v, int64_t stamp) {
     st->done = v;
-    if (st->hdone) {
-        __hip_atomic_store(st->hdone, st->hgen | stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __threadfence_system();
-    }
+    if (st->hdone) done_stamp_store(st->hdone, st->hgen, stamp);
 }
 
 // the solver state after the init sums bb = b.b and ur = u.r (PCGSolver.py:86-105)

@@ -61,8 +61,8 @@ constexpr int kTimedSlots = 64;   // sampled SpMV timing event pairs of one solv
 // (VERDICT r3 weak #3). One solve at a time per device: `solve_mu` is held by psk_pcg/psk_gmres.
 struct SolveKit {
     bool ready = false;
-    uint64_t solve_gen = 0;       // PCG solves started (tags the done stamps, pcg.hip set_done)
-    int64_t *hmap = nullptr;      // host-mapped coherent words the kernels write (PCG done stamp at [0])
+    uint64_t solve_gen = 0;       // solves started (tags the done stamps, solve_loop.hpp StampPoll)
+    int64_t *hmap = nullptr;      // host-mapped coherent words the kernels write (the done stamp at [0])
     void *hstage = nullptr;       // pinned staging for the end-of-solve state / error-word copies (4 KiB)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // loop_ms (timing)
     hipEvent_t fev[kPollSlots] = {};           // poll chunks (no timing)
@@ -427,6 +427,14 @@ __device__ __forceinline__ double reduce_partials(const double *part, int np, in
     double v = 0.0;
     for (int i = threadIdx.x; i < np; i += kBlock) v += part[(int64_t)i * stride];
     return block_sum(v, sh);
+}
+
+// The done stamp of a device-loop solver (solve_loop.hpp, StampPoll): one thread stores the solve's generation and
+// the stamp into the host-mapped word at system scope and drains the store before its kernel ends, so the host
+// reads it once an event recorded behind that kernel has completed.
+__device__ __forceinline__ void done_stamp_store(int64_t *hdone, int64_t hgen, int64_t stamp) {
+    __hip_atomic_store(hdone, hgen | stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
 }
 
 // ---------------------------------------------------------------------------------------------

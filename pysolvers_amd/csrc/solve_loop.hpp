@@ -1,5 +1,6 @@
-// solve_loop.hpp — host-side helpers of the device-loop solvers (psk_pcg, psk_gmres, psk_vcycle): the workspace
-// carver and the done-stamp poll. Host code only: no kernel lives here.
+// solve_loop.hpp — host-side helpers of the device-loop solvers (psk_pcg, psk_bicgstab, psk_gmres, psk_vcycle): the
+// workspace carver and the done-stamp poll, both used by all four. Host code only: no kernel lives here (the
+// kernels' side of the stamp is done_stamp_store, psk_internal.hpp).
 #pragma once
 #include "psk_internal.hpp"
 
@@ -38,10 +39,10 @@ struct GmresView {
 };
 int gmres_work_view(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool grow, GmresView *v);
 
-// The done stamp (set_done, pcg_state.hpp; vc_check_kernel): k + 2 for a kernel of iteration k, 1 for the init
-// (0 = running) — a system-scope store to a host-mapped word, drained before the kernel ends, so once an event
-// recorded after this kernel has completed the host reads the word directly, with no per-chunk device-to-host
-// copy (a blit kernel) on the solver's stream. The stamp lets the host act on the state as of the chunk it waited
+// The done stamp (done_stamp_store, called by the kernel of each solver that ends its loop): k + 2 for a kernel of
+// iteration k (psk_gmres: step k of the current cycle), 1 for the init (0 = running) — a system-scope store to a
+// host-mapped word, drained before the kernel ends, so once an event recorded after this kernel has completed the
+// host reads the word directly, with no per-chunk device-to-host copy (a blit kernel) on the solver's stream. The stamp lets the host act on the state as of the chunk it waited
 // for, not a later one its GPU has already run: every rank of a sharded solve then stops after the same chunk and
 // enqueues the same collectives.
 // The word is shared by every solve on the device; each solve tags its stamps with its own generation (high

@@ -51,10 +51,7 @@ __global__ void vc_init_kernel(const double *bb, VcState *st, int64_t *hdone, in
     st->nhist = 0;
     st->resid = 0.0;
     st->normB = normB;
-    if (normB == 0.0) {
-        __hip_atomic_store(hdone, hgen | 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __threadfence_system();
-    }
+    if (normB == 0.0) done_stamp_store(hdone, hgen, 1);
 }
 
 // After cycle k and r = b - A x (sum = ||r||^2, published by the SpMV's launch). Every block reads the same words
@@ -90,8 +87,7 @@ __global__ __launch_bounds__(kBlock) void vc_check_kernel(int64_t n, const doubl
     st->resid = normR;
     if (hit) {
         st->conv_iter = k;
-        __hip_atomic_store(hdone, hgen | (k + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // as set_done
-        __threadfence_system();
+        done_stamp_store(hdone, hgen, k + 2);
     }
 }
 

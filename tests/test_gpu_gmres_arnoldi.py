@@ -15,7 +15,10 @@ Bars (written here, not inferred from the device):
     history entry against the host's ||b - A x|| to 1e-10 ||b||.
 (g) exact Arnoldi breakdowns (every intermediate 0, +-1 or a power of two, one nonzero term per sum): history and x
     are krylov.gmres's bits.
-(h) the steps the host enqueues behind convergence (its poll lags by two steps) leave the workspace untouched.
+(h) the steps the host enqueues behind convergence (its poll lags by two steps) leave the workspace untouched, and
+    their number is the one that lag gives: spmv_launches, iters, hist_len, exit and status against krylov's solve
+    where the cycle ends inside the lag, just past it, never, and in a later cycle; b = 0 enqueues no step, and the
+    solve behind it repeats the bits of the one before.
 psk_gmres never clears its basis or its rotations, so every solve here runs on a workspace psk_lab_gmres_prefill
 zeroed: what is zero afterwards was not written.
 
@@ -376,6 +379,66 @@ def test_steps_enqueued_behind_convergence_leave_no_trace(psk):
     # ... and without the zeroed workspace (what the basis holds beforehand is never read)
     res3, x3, hist3 = dev.solve(_rhs("rand513"), prefill=False)
     assert np.array_equal(_bits(hist3[:kc + 1]), _bits(hist[:kc + 1])) and np.array_equal(_bits(x3), _bits(x))
+
+
+def _diag7():
+    A = sp.diags(2.0 ** np.arange(-3, 4)).tocsr()
+    b = np.zeros(7)
+    b[5] = 3.0
+    return A, b
+
+
+# name -> (system, preconditioner, maxiter, restart, tau, the exit taken); FD17 is _run's solve
+HOST_LOOP = {"diag7_maxiter50": (_diag7, "jacobi", 50, 0, 1e-12, "ARNOLDI_BREAKDOWN"),   # kc = 0, inside the lag
+             "diag7_maxiter2": (_diag7, "jacobi", 2, 0, 1e-12, "ARNOLDI_BREAKDOWN"),     # Kc < kc + 3
+             "shift4": (_shift4, "identity", 50, 0, 1e-12, "ARNOLDI_BREAKDOWN"),         # kc = 3 = lag + 1
+             "shift4_gmres2": (_shift4, "identity", 50, 2, 1e-12, "MAXITER"),            # 25 full cycles
+             FD17: (lambda: (_matrix(FD17), _rhs(FD17)), "cheb", MAXITER, 5, TAU, "TOLERANCE")}
+
+
+def _spmvs_enqueued(iters, converged, maxiter, restart):
+    """The SpMVs psk_gmres enqueues. The host learns of `done` two steps late: a cycle of Kc steps that converged at
+    its step kc enqueued min(Kc, kc + 3) Arnoldi SpMVs, any other cycle Kc; every restart cycle starts with the
+    residual's SpMV, and a convergence exit ends with the true residual's."""
+    K = max(1, restart if 0 < restart < maxiter else maxiter)
+    if not converged:
+        return maxiter + (maxiter + K - 1) // K - 1
+    full, kc = divmod(iters - 1, K)
+    return full * K + min(min(K, maxiter - full * K), kc + 3) + full + 1
+
+
+@pytest.mark.parametrize("name", list(HOST_LOOP))
+def test_host_loop_counts_and_the_done_stamp(psk, name):
+    """What the host enqueued (spmv_launches) and reported, against krylov's solve; then b = 0 on the same matrix
+    (no step, no SpMV), and the first solve again behind it: the same bits, so no stamp outlives its solve."""
+    system, prec, maxiter, restart, tau, exit_name = HOST_LOOP[name]
+    A, b = system()
+    M = _minv(FD17) if prec == "cheb" else krylov.jacobi_form(A) if prec == "jacobi" else krylov.identity_apply
+    ref = (krylov.gmres_restarted(A, b, restart, maxiter=maxiter, tau=tau, precond=M) if restart else
+           krylov.gmres(A, b, maxiter=maxiter, tau=tau, precond=M))
+    if name == FD17:
+        dev, res, x, hist, _ = _run(psk, name)
+    else:
+        dev = Device(psk, A, prec)
+        res, x, hist = dev.solve(b, maxiter=maxiter, tau=tau, restart=restart)
+    N = dev.N
+    want_exit = getattr(N, "PSK_EXIT_" + exit_name)
+    want = _spmvs_enqueued(ref["iters"], want_exit != N.PSK_EXIT_MAXITER, maxiter, restart)
+    print("%s: iters %d (oracle %d) hist_len %d exit %d status %d spmv_launches %d (formula %d)"
+          % (name, res.iters, ref["iters"], res.hist_len, res.exit, res.status, res.spmv_launches, want))
+    assert res.iters == ref["iters"] and res.hist_len == len(ref["hist"])
+    assert res.exit == want_exit and bool(res.success) == ref["success"]
+    assert res.status == (N.PSK_CONVERGED if ref["success"] else N.PSK_MAXITER)
+    assert res.spmv_launches == want
+    res0, x0, hist0 = dev.solve(np.zeros_like(b), maxiter=maxiter, tau=tau, restart=restart)
+    assert (res0.spmv_launches, res0.iters, res0.hist_len) == (0, 1, 0)
+    assert res0.success and res0.status == N.PSK_CONVERGED and res0.exit == N.PSK_EXIT_NONE and res0.norm_b == 0.0
+    assert not x0.any() and np.all(np.isnan(hist0))
+    res2, x2, hist2 = dev.solve(b, maxiter=maxiter, tau=tau, restart=restart)
+    assert (res2.iters, res2.hist_len, res2.exit, res2.status, res2.spmv_launches) == \
+        (res.iters, res.hist_len, res.exit, res.status, res.spmv_launches)
+    assert np.array_equal(_bits(x2), _bits(x))
+    assert np.array_equal(_bits(hist2[:res.hist_len]), _bits(hist[:res.hist_len]))
 
 
 def test_every_kind_of_rhs_gives_the_same_bits(psk):

@@ -17,7 +17,7 @@ from pysolvers_amd import _native as N
 PCG, GMRES, VCYCLE = 0, 1, 2
 GEN, OWN_X, DEV_IO = 1, 2, 4
 MAX_GRID = 2048          # kMaxGrid
-STATE = 256              # sizeof(PcgState) (80) and sizeof(GmresState) (48) rounded up to 256
+STATE = 256              # sizeof(PcgState) (80) and sizeof(GmresState) (64) rounded up to 256
 VC_STATE = 64            # sizeof(VcState)
 VC_TICK = 65 * 64 * 4    # (kVcGroups + 1) counters, one per 256-byte line
 
@@ -106,7 +106,7 @@ def test_gmres_layout(gen, restart, maxiter):
         assert size[0] == qbytes + (5 if gen else 3) * vec
         check(offs[:nbig], ext, size[0])
         hb =up(ld * K * 8)
-        ext = [48, ld * K * 8, ld * K * 8, 2 * K * 8, ld * 8, MAX_GRID * 8, (maxiter + 1) * 8, ld * 8, (K + 2) * 8]
+        ext = [64, ld * K * 8, ld * K * 8, 2 * K * 8, ld * 8, MAX_GRID * 8, (maxiter + 1) * 8, ld * 8, (K + 2) * 8]
         small = STATE + 2 * hb + up(2 * K * 8) + up(ld * 8) + up(MAX_GRID * 8) + up((maxiter + 1) * 8) + up(ld * 8) + \
             up((K + 2) * 8)
         want, s = [], 0
