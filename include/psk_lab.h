@@ -37,8 +37,8 @@ int psk_lab_trisolve_workers(const psk_prec *M, int32_t which, int32_t *enrolled
 int psk_lab_trisolve_plan(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, int32_t upper,
                           int32_t unit, const int32_t *nat, int32_t num_cus, int64_t syncfree_waves, int32_t *schedule,
                           double *est, int64_t *info);
-/* Lab / tests of the AMG smoother's paired Gauss-Seidel sweeps (round 6, amg.hip gs_pair_kernel): set = 0 runs
- * every level's sweeps one launch each (the serialized path), 1 pairs them on the levels that qualify, -1
+/* Lab / tests of the AMG smoother's paired Gauss-Seidel sweeps (round 6, amg_gs_pair.hip gs_pair_kernel): set = 0
+ * runs every level's sweeps one launch each (the serialized path), 1 pairs them on the levels that qualify, -1
  * leaves the setting; *levels_on = the levels pairing now, *levels_eligible = the levels that qualify. */
 int psk_lab_amg_gs_pair(psk_prec *M, int32_t set, int32_t *levels_on, int32_t *levels_eligible);
 /* Lab (round 6): back-to-back SpMV launches (dot = 0: plain y = A x; 1: the PCG loop's kSpmvDot launch) that cycle

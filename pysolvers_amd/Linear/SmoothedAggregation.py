@@ -2,8 +2,8 @@
 
 The reference's BuildAggregates is quadratic (phase 2 scans every aggregate for every remaining
 node; 253 s at FD 512^2). Here aggregation and the filtered matrix come from
-``psk_sa_aggregate`` (C++, pysolvers_amd/csrc/amg.hip) with identical results, and the remaining
-steps use the same scipy operations the reference uses, so P, R and every coarse operator are
+``psk_sa_aggregate`` (C++, pysolvers_amd/csrc/amg_aggregate.hip) with identical results, and the
+remaining steps use the same scipy operations the reference uses, so P, R and every coarse operator are
 bit-identical to the reference's (tests: oracle/amg.py is pinned against the reference; the CPU
 tests check this module against oracle/amg.py).
 

@@ -3,6 +3,7 @@
 // CUs while a solve runs (the forward-progress tests, tests/test_gpu_progress.py), a dispatch probe and the
 // enrolment count of the last sync-free triangular-solve launch. Declared in include/psk_lab.h; nothing in the
 // product path calls them.
+#include "amg.hpp"
 #include "trisolve.hpp"
 #include "pcg_state.hpp"
 #include "solve_loop.hpp"

@@ -1,6 +1,6 @@
 // prec.hip — the preconditioner handle: Jacobi (jacobi_dinv_kernel, scale_kernel), the generic device apply
-// every Krylov driver calls (prec_apply_dev) and the psk_prec_* ABI (create, apply, destroy, info).
-#include "psk_internal.hpp"
+// every Krylov driver calls (prec_apply_dev, prec_check_error) and the psk_prec_* ABI (create, apply, destroy, info).
+#include "amg.hpp"
 
 #include <cstdlib>
 
@@ -40,6 +40,20 @@ int prec_apply_dev(const psk_prec *M, int64_t n, const double *v, double *out, h
     if (M->kind == PSK_PREC_DENSE) return dense_apply(M, v, out, s);
     if (M->kind == PSK_PREC_CHEBYSHEV) return cheby_apply(M, v, out, s);
     return fail(PSK_ERR_UNSUPPORTED, "unknown preconditioner kind");
+}
+
+int prec_check_error(const psk_prec *M, hipStream_t s) {
+    if (!M) return PSK_OK;
+    if (M->kind == PSK_PREC_ILU) return ilu_check_error(M, s);
+    if (M->kind == PSK_PREC_DENSE) return dense_check_error(M, s);
+    if (M->kind == PSK_PREC_AMG) {
+        const AmgHierarchy *h = M->amg;
+        for (psk_prec *S : h->S)
+            if (S && S->kind == PSK_PREC_ILU) PSK_TRY(ilu_check_error(S, s));
+        if (h->coarse && h->coarse->kind == PSK_PREC_ILU) PSK_TRY(ilu_check_error(h->coarse, s));
+        if (h->coarse && h->coarse->kind == PSK_PREC_DENSE) PSK_TRY(dense_check_error(h->coarse, s));
+    }
+    return PSK_OK;
 }
 
 }  // namespace psk

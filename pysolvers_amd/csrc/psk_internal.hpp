@@ -313,7 +313,7 @@ struct TriFactor {
         int W = 0, R = 0, KM = 0;
         void release();
     } lv;
-    // 5-point grid signature of an upper factor (detect_fd5; amg.hip's paired Gauss-Seidel sweeps): n = fd5_m * H,
+    // 5-point grid signature of an upper factor (detect_fd5; amg_gs_pair.hip's paired sweeps): n = fd5_m * H,
     // row i's off-diagonal entries exactly columns i + 1 (i % m < m - 1) and i + m (i + m < n), values fd5_a1 / fd5_am,
     // every diagonal fd5_d, fd5_mfirst = the +m entry stored before the +1 entry. fd5_m = 0: no such signature.
     int64_t fd5_m = 0;
@@ -963,23 +963,8 @@ int fd2d_fill(psk_csr *A, int64_t m, double a, double b, int64_t row_begin, int6
 // generic preconditioner apply (device pointers, out must not alias v): identity copy, Jacobi, ILU
 int prec_apply_dev(const psk_prec *M, int64_t n, const double *v, double *out, hipStream_t s);
 int ilu_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);
-int ilu_apply_add(const psk_prec *M, const double *v, double *x, hipStream_t s);
-// AMG paired Gauss-Seidel sweeps (amg.hip; the lab library's switch): set -1 / 0 / 1, counts out
-int amg_gs_pair(psk_prec *M, int set, int *on, int *eligible);   // x += M^-1 v
+int ilu_apply_add(const psk_prec *M, const double *v, double *x, hipStream_t s);   // x += M^-1 v
 int ilu_check_error(const psk_prec *M, hipStream_t s);
-int amg_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);
-void amg_free(AmgHierarchy *h);
-// the V-cycle loop's pieces, shared by amg_apply and psk_vcycle (vcycle.hip): the finest level's matrix, iterate
-// and residual, ||b||^2 (normb2[0]), the residual SpMV's sum (sum[0]) and the solver's own grow-only device words
-struct AmgLoop {
-    psk_csr *A;
-    double *x, *r, *normb2, *sum;
-    DevBuf *work;
-};
-int amg_loop_view(const psk_prec *M, AmgLoop *out);
-int amg_loop_start(const psk_prec *M, const Context *c, const double *v, hipStream_t s);   // ||v||^2, x = copy(v)
-int amg_cycle(const psk_prec *M, const Context *c, const double *v, hipStream_t s);        // x = runCycle(v, x)
-int amg_residual(const psk_prec *M, const double *v, hipStream_t s);                       // r = v - A x, ||r||^2
 int dense_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);
 int dense_check_error(const psk_prec *M, hipStream_t s);
 void dense_free(DenseInverse *d);

@@ -451,7 +451,7 @@ int split_factor(int64_t n, const int32_t *rp, const int32_t *ci, const double *
 namespace {
 
 // The 5-point grid signature of an upper factor (TriFactor::fd5_*): triu of a 5-point operator on an m x H grid
-// with one value per diagonal. amg.hip fuses two Gauss-Seidel sweeps of such a level into one launch.
+// with one value per diagonal. amg_gs_pair.hip fuses two Gauss-Seidel sweeps of such a level into one launch.
 static void detect_fd5(int64_t n, const std::vector<int32_t> &rp, const std::vector<int32_t> &ci,
                        const std::vector<double> &va, const std::vector<double> &dg, TriFactor &T) {
     T.fd5_m = 0;

@@ -13,6 +13,7 @@
 // and reads the done word behind an event kVcLag chunks back (solve_loop.hpp StampPoll). By default (check_every 1,
 // kVcLag 1) at most one cycle past the converging one is enqueued; cycles that run after it find conv_iter >= 0
 // and change neither the output, the history nor the state, so the results do not depend on the lag.
+#include "amg.hpp"
 #include "pcg_state.hpp"
 
 #include <cmath>

@@ -116,8 +116,8 @@ def test_configs4_amg_hierarchy_and_pcg_fd8192(psk):
     yu, yv, yuv = M.applyRight(u), M.applyRight(v), M.applyRight(u + 2.0 * v)
     assert np.all(np.isfinite(yuv))
     assert np.linalg.norm(yuv - (yu + 2.0 * yv)) <= 1e-10 * np.linalg.norm(yuv)
-    # round 6: the fine level's Gauss-Seidel sweeps run two per launch (amg.hip gs_pair_kernel); at full size the
-    # apply and the PCG+AMG trajectory equal the serialized sweeps' bit for bit (psk_lab_amg_gs_pair switches)
+    # round 6: the fine level's Gauss-Seidel sweeps run two per launch (amg_gs_pair.hip gs_pair_kernel); at full size
+    # the apply and the PCG+AMG trajectory equal the serialized sweeps' bit for bit (psk_lab_amg_gs_pair switches)
     import ctypes
     from pysolvers_amd import _native as N
     lab = N.load_lab()

@@ -1,4 +1,4 @@
-"""The AMG smoother's paired Gauss-Seidel sweeps (round 6, amg.hip gs_pair_kernel) against the serialized
+"""The AMG smoother's paired Gauss-Seidel sweeps (round 6, amg_gs_pair.hip gs_pair_kernel) against the serialized
 sweeps: two sweeps x <- x + triu(A)^-1 (f - A x) (ClassicSmoothers.py:31-36) in one launch on 5-point grid
 levels. Bar: BITWISE equality of the AMG apply with pairing on and off (psk_lab_amg_gs_pair switches it), on
 square and rectangular grids whose band split (63 lines per band) leaves full, partial and one-line bands,

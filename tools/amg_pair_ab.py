@@ -1,4 +1,4 @@
-"""A/B of the AMG smoother's paired Gauss-Seidel sweeps (amg.hip gs_pair_kernel) on configs[4]'s workload:
+"""A/B of the AMG smoother's paired Gauss-Seidel sweeps (amg_gs_pair.hip gs_pair_kernel) on configs[4]'s workload:
 -FD 8192^2, AMG(numIters=2, numLevels=5, nuPre=2, nuPost=2, Gauss-Seidel). Alternates pairing on / off
 (psk_lab_amg_gs_pair) on the same hierarchy: AMG apply time (median of 5), PCG+AMG iterations per second
 (6 iterations per solve, tau = 0), and whether the two applies agree bitwise. One JSON line on stdout.

@@ -1,4 +1,5 @@
-"""Per-band timeline of the AMG smoother's paired Gauss-Seidel launch (amg.hip gs_pair_kernel) from a profile build:
+"""Per-band timeline of the AMG smoother's paired Gauss-Seidel launch (amg_gs_pair.hip gs_pair_kernel) from a profile
+build:
     bash scripts/build_variant.sh gpprof -DPSK_GP_PROF
     PSK_LIBRARY=tools/bin/ab_gpprof/libpsk.so python tools/gp_prof.py [--m 8192]
 Runs AMG applies on -FD m^2 (5 levels) and reads the last launch's per-band records: start lag between
