@@ -333,21 +333,74 @@ static void bicg_layout(Carve &big, Carve &sm, int64_t n, int64_t maxiter, bool 
     w.sums = sm.take<double>(8 * 8);   // rhat.v, t.s, t.t, [r.r, rhat.r], s.s, b.b, ||b - A x||^2
     w.hist = sm.take<double>((size_t)(maxiter + 1) * 8);
 }
+void bicgstab_layout_probe(int64_t n, int64_t maxiter, bool gen, std::vector<int64_t> *log, int64_t *bytes) {
+    Carve big, sm;
+    big.log = sm.log = log;
+    BicgWork w;
+    bicg_layout(big, sm, n, maxiter, gen, w);
+    bytes[0] = big.off > 0 ? (int64_t)big.off : 256;
+    bytes[1] = (int64_t)sm.off;
+}
 
-static void bicg_msg(psk_result *res, const char *m) { std::snprintf(res->msg, sizeof(res->msg), "%s", m); }
-
+// what the phases of one solve share
 struct BicgRun {
     psk_csr *A;
     const psk_prec *M;
     const psk_ctl *ctl;
     Context *c;
+    SolveKit *kit;
     hipStream_t s;
     int64_t n, nv;
+    int C;           // iterations per poll chunk
     bool gen;
     const double *dinv;
     BicgWork w;
     GridSum gsB, gsD, gsE;
 };
+
+static int bicg_workspace(BicgRun &r) {
+    int64_t need[2];
+    bicgstab_layout_probe(r.n, r.ctl->maxiter, r.gen, nullptr, need);
+    PSK_TRY(r.A->ws.ensure((size_t)need[0]));
+    PSK_TRY(r.A->ws_small.ensure((size_t)need[1]));
+    Carve big{r.A->ws.as<char>()}, sm{r.A->ws_small.as<char>()};
+    bicg_layout(big, sm, r.n, r.ctl->maxiter, r.gen, r.w);
+    return PSK_OK;
+}
+
+// everything in front of the loop: the gridsums, the state, b, x0 = 0 and the init launch (b.b). *run: iterations
+// may be enqueued (false: the stamp already says b = 0; only the general path waits to learn it)
+static int bicg_init(BicgRun &r, StampPoll &poll, const double *b, int32_t loc, bool *run) {
+    BicgWork &w = r.w;
+    hipStream_t s = r.s;
+    const int64_t n = r.n;
+    GridSum gs0;
+    PSK_TRY(gridsum_prepare(r.c, r.nv, 2, w.sums + kBicgRr, &r.gsE));
+    PSK_TRY(gridsum_prepare(r.c, r.nv, 1, w.sums + kBicgSs, &r.gsB));
+    PSK_TRY(gridsum_prepare(r.c, r.nv, 1, w.sums + kBicgTt, &r.gsD));
+    // the init sums b.b over the SpMV's tiles (launch_spmv: 256-row slices, or tile_rows rows in the CSR layout)
+    const int trows = (r.A->sl_off || r.A->dg_mask) ? kBlock : r.A->tile_rows;
+    const int64_t nwg = (n + trows - 1) / trows;
+    PSK_TRY(gridsum_prepare(r.c, nwg, 1, w.sums + kBicgBb, &gs0));
+    PSK_HIP(hipMemsetAsync(w.st, 0, sizeof(BicgState), s));
+    PSK_TRY(to_device_vec(b, loc, n, w.bv, s));
+    PSK_HIP(hipMemsetAsync(w.x, 0, (size_t)n * 8, s));
+    PSK_HIP(hipEventRecord(r.kit->ev0, s));
+    hipLaunchKernelGGL(bicg_init_kernel, dim3((unsigned)nwg), dim3(kBlock), 0, s, n, trows, w.bv, gs0,
+                       BicgInitFin{r.ctl->tau, r.ctl->norm_b, w.st, poll.hdone(), poll.hgen()});
+    PSK_HIP(hipGetLastError());
+    *run = true;
+    if (r.gen) {
+        // The preconditioner's kernels do not test `done`: they run in every iteration the host enqueues, also
+        // behind the one that ended the solve. So they only ever see defined vectors: p_0 is stored (the other
+        // paths read b), s starts at zero, and a b = 0 solve enqueues no iteration at all.
+        PSK_HIP(hipMemcpyAsync(w.p, w.bv, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+        PSK_HIP(hipMemsetAsync(w.s, 0, (size_t)n * 8, s));
+        PSK_TRY(poll.wait(s));
+        *run = poll.stamp() == 0;
+    }
+    return PSK_OK;
+}
 
 // iteration k: [ph], S1, B, [sh], S2, D, E, F
 static int bicg_iteration(BicgRun &r, int64_t k) {
@@ -356,7 +409,7 @@ static int bicg_iteration(BicgRun &r, int64_t k) {
     const int64_t n = r.n;
     const dim3 g((unsigned)r.nv), blk(kBlock);
     const int32_t *done = &w.st->done;
-    // r_0 = p_0 = rhat = b: iteration 0 reads b in their place (general path: p_0 was copied, bicg_solve)
+    // r_0 = p_0 = rhat = b: iteration 0 reads b in their place (general path: p_0 was copied, bicg_init)
     const double *rk = k == 0 ? w.bv : w.r, *pk = k == 0 && !r.gen ? w.bv : w.p;
     const int smode = r.dinv ? kSpmvJacobiDot : kSpmvPlainDot;
     if (r.gen) {
@@ -389,93 +442,55 @@ static int bicg_iteration(BicgRun &r, int64_t k) {
     return PSK_OK;
 }
 
-static int bicg_solve(BicgRun &r, const double *b, double *xout, psk_result *res, double *hist, int32_t loc) {
-    psk_csr *A = r.A;
-    const psk_ctl *ctl = r.ctl;
-    hipStream_t s = r.s;
-    const int64_t n = r.n, maxiter = ctl->maxiter;
-    Carve big0, sm0;
-    BicgWork w0;
-    bicg_layout(big0, sm0, n, maxiter, r.gen, w0);
-    PSK_TRY(A->ws.ensure(big0.off > 0 ? big0.off : 256));
-    PSK_TRY(A->ws_small.ensure(sm0.off));
-    Carve big{A->ws.as<char>()}, sm{A->ws_small.as<char>()};
-    bicg_layout(big, sm, n, maxiter, r.gen, r.w);
+// done by the tolerance test on a non-zero b: the exit whose true residual ||b - A x|| is measured and reported
+static bool bicg_tol_exit(const BicgState &hs) { return hs.done == 1 && !hs.zero_b && hs.by_tol; }
+
+// behind the loop: the state; what the exit left to do on the device (the half step's x += alpha ph, the true
+// residual into *true_sq); the checks of the in-launch reductions and loop_ms
+static int bicg_finish(BicgRun &r, BicgState *hs, double *true_sq, psk_result *res) {
     BicgWork &w = r.w;
-    SolveKit *kit;
-    PSK_TRY(solve_kit(r.c, false, &kit));
-    StampPoll poll(kit);
-    GridSum gs0;
-    PSK_TRY(gridsum_prepare(r.c, r.nv, 2, w.sums + kBicgRr, &r.gsE));
-    PSK_TRY(gridsum_prepare(r.c, r.nv, 1, w.sums + kBicgSs, &r.gsB));
-    PSK_TRY(gridsum_prepare(r.c, r.nv, 1, w.sums + kBicgTt, &r.gsD));
-    // the init sums b.b over the SpMV's tiles (launch_spmv: 256-row slices, or tile_rows rows in the CSR layout)
-    const int trows = (A->sl_off || A->dg_mask) ? kBlock : A->tile_rows;
-    const int64_t nwg = (n + trows - 1) / trows;
-    PSK_TRY(gridsum_prepare(r.c, nwg, 1, w.sums + kBicgBb, &gs0));
-    PSK_HIP(hipMemsetAsync(w.st, 0, sizeof(BicgState), s));
-    PSK_TRY(to_device_vec(b, loc, n, w.bv, s));
-    PSK_HIP(hipMemsetAsync(w.x, 0, (size_t)n * 8, s));
-    PSK_HIP(hipEventRecord(kit->ev0, s));
-    hipLaunchKernelGGL(bicg_init_kernel, dim3((unsigned)nwg), dim3(kBlock), 0, s, n, trows, w.bv, gs0,
-                       BicgInitFin{ctl->tau, ctl->norm_b, w.st, poll.hdone(), poll.hgen()});
-    PSK_HIP(hipGetLastError());
-    bool run = true;
-    if (r.gen) {
-        // The preconditioner's kernels do not test `done`: they run in every iteration the host enqueues, also
-        // behind the one that ended the solve. So they only ever see defined vectors: p_0 is stored (the other
-        // paths read b), s starts at zero, and a b = 0 solve enqueues no iteration at all.
-        PSK_HIP(hipMemcpyAsync(w.p, w.bv, (size_t)n * 8, hipMemcpyDeviceToDevice, s));
-        PSK_HIP(hipMemsetAsync(w.s, 0, (size_t)n * 8, s));
-        PSK_TRY(poll.wait(s));
-        run = poll.stamp() == 0;
-    }
-    const int C = ctl->check_every > 0 ? ctl->check_every : (n >= (1 << 20) ? 2 : 16);
-    int64_t launched = 0;
-    for (int64_t k = 0; run && k < maxiter; ++k) {
-        bool stop;
-        PSK_TRY(poll.step<2>(k, C, s, &stop));
-        if (stop) break;
-        PSK_TRY(bicg_iteration(r, k));
-        launched = k + 1;
-    }
-    BicgState hs;
-    PSK_HIP(hipMemcpyAsync(&hs, w.st, sizeof(hs), hipMemcpyDeviceToHost, s));
+    hipStream_t s = r.s;
+    PSK_HIP(hipMemcpyAsync(hs, w.st, sizeof(*hs), hipMemcpyDeviceToHost, s));
     PSK_HIP(hipStreamSynchronize(s));
-    // SpMV launches that did their work (those enqueued behind `done` returned at once)
-    int64_t spmvs = hs.done == 0 ? 2 * launched : hs.zero_b ? 0 : hs.half || hs.brk_kind == 1 ? 2 * hs.iters + 1 : 2 * hs.iters + 2;
-    double true_sq = 0.0;
-    const bool tol_exit = hs.done == 1 && !hs.zero_b && hs.by_tol;
-    if (hs.done == 1 && hs.half) {
+    if (hs->done == 1 && hs->half) {
         // general path: the iterations enqueued behind the exit recomputed ph from the same p (F returned), the
         // same bits
-        hipLaunchKernelGGL(bicg_half_x_kernel, dim3((unsigned)r.nv), dim3(kBlock), 0, s, n, w.x,
-                           r.gen ? w.ph : (hs.iters == 0 ? w.bv : w.p), r.gen ? nullptr : r.dinv, w.st);
+        hipLaunchKernelGGL(bicg_half_x_kernel, dim3((unsigned)r.nv), dim3(kBlock), 0, s, r.n, w.x,
+                           r.gen ? w.ph : (hs->iters == 0 ? w.bv : w.p), r.gen ? nullptr : r.dinv, w.st);
         PSK_HIP(hipGetLastError());
     }
-    if (tol_exit) {   // the true residual ||b - A x|| (t is free by now)
-        PSK_TRY(launch_spmv(A, kSpmvResid, w.x, w.t, nullptr, w.bv, w.sums + kBicgTrue, nullptr, s));
-        ++spmvs;
-        PSK_HIP(hipMemcpyAsync(&true_sq, w.sums + kBicgTrue, 8, hipMemcpyDeviceToHost, s));
+    *true_sq = 0.0;
+    if (bicg_tol_exit(*hs)) {   // t is free by now
+        PSK_TRY(launch_spmv(r.A, kSpmvResid, w.x, w.t, nullptr, w.bv, w.sums + kBicgTrue, nullptr, s));
+        PSK_HIP(hipMemcpyAsync(true_sq, w.sums + kBicgTrue, 8, hipMemcpyDeviceToHost, s));
     }
-    PSK_HIP(hipEventRecord(kit->ev1, s));
+    PSK_HIP(hipEventRecord(r.kit->ev1, s));
     PSK_HIP(hipStreamSynchronize(s));
     // an expired in-launch reduction wait poisons a sum with NaN; report it as the error it is
     PSK_TRY(gridsum_check(r.c));
     if (r.gen) PSK_TRY(prec_check_error(r.M, s));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, kit->ev0, kit->ev1);
-    res->loop_ms = ms;
+    res->loop_ms = loop_ms(r.kit);
+    return PSK_OK;
+}
+
+// SpMV launches of the loop that did their work (those enqueued behind `done` returned at once)
+static int64_t bicg_spmv_count(const BicgState &hs, int64_t launched) {
+    if (hs.done == 0) return 2 * launched;                      // still running: every enqueued iteration ran S1 and S2
+    if (hs.zero_b) return 0;                                    // b = 0: the init raised `done`
+    if (hs.half || hs.brk_kind == 1) return 2 * hs.iters + 1;   // B of iteration `iters` raised it: S2 returned at once
+    return 2 * hs.iters + 2;                                    // E of iteration `iters` raised it: both had run
+}
+
+// The state hs of a finished loop that enqueued `launched` iterations, decoded into res; the history and x.
+static int bicg_report(const BicgRun &r, const BicgState &hs, int64_t launched, double true_sq, psk_result *res,
+                       double *hist, double *xout, int32_t loc) {
+    const int64_t maxiter = r.ctl->maxiter;
     res->norm_b = hs.normB;
-    res->spmv_launches = spmvs;
+    res->spmv_launches = bicg_spmv_count(hs, launched) + (bicg_tol_exit(hs) ? 1 : 0);   // + the true residual's
     res->resid_recursive = hs.rec;
     int64_t nh = hs.nhist;
-    if (hs.zero_b) {   // b = 0: x = 0, as psk_pcg reports it
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-        res->iters = 1;
-        res->resid = 0.0;
-        res->exit = PSK_EXIT_NONE;
+    if (hs.zero_b) {   // b = 0: x = 0 and resid = 0, as psk_pcg reports it
+        result_trivial(res);
         nh = 0;
     } else if (hs.done == 1) {
         res->iters = hs.iters + 1;
@@ -483,7 +498,7 @@ static int bicg_solve(BicgRun &r, const double *b, double *xout, psk_result *res
         res->success = 1;
         res->resid = hs.rec;
         res->exit = hs.by_tol ? PSK_EXIT_TOLERANCE : PSK_EXIT_MAXITER;
-        if (tol_exit) {
+        if (bicg_tol_exit(hs)) {
             const double tr = std::sqrt(true_sq);
             res->resid = tr;
             if (!(tr <= hs.tauNormB)) {
@@ -492,7 +507,7 @@ static int bicg_solve(BicgRun &r, const double *b, double *xout, psk_result *res
                 std::snprintf(res->msg, sizeof(res->msg),
                               "BiCGStab failure: true residual %12.5g did not meet tolerance tau=%12.5g. "
                               "Recursive residual was %12.5g.",
-                              tr, ctl->tau, hs.rec);
+                              tr, r.ctl->tau, hs.rec);
             }
         }
     } else if (hs.done == 2) {
@@ -501,24 +516,45 @@ static int bicg_solve(BicgRun &r, const double *b, double *xout, psk_result *res
         res->success = 0;
         res->iters = hs.iters;
         res->resid = NAN;
-        bicg_msg(res, hs.brk_kind == 1   ? "breakdown dot(rhat,v)==0"
-                      : hs.brk_kind == 2 ? "breakdown dot(t,t)==0"
-                      : hs.brk_kind == 3 ? "breakdown omega==0"
-                                         : "breakdown dot(rhat,r)==0");
+        result_msg(res, hs.brk_kind == 1   ? "breakdown dot(rhat,v)==0"
+                        : hs.brk_kind == 2 ? "breakdown dot(t,t)==0"
+                        : hs.brk_kind == 3 ? "breakdown omega==0"
+                                           : "breakdown dot(rhat,r)==0");
     } else {   // maxiter reached: handleMaxiter(maxiter - 1, ...), as psk_pcg
         res->status = PSK_MAXITER;
         res->exit = PSK_EXIT_MAXITER;
         res->success = 0;
         res->iters = maxiter > 0 ? maxiter - 1 : 0;
         res->resid = hs.rec;
-        bicg_msg(res, "failure to converge");
+        result_msg(res, "failure to converge");
     }
     if (nh > maxiter) nh = maxiter;
     res->hist_len = nh;
-    if (hist && nh > 0) PSK_HIP(hipMemcpy(hist, w.hist, (size_t)nh * 8, hipMemcpyDeviceToHost));
-    PSK_TRY(from_device_vec(w.x, loc, n, xout, s));
-    PSK_HIP(hipStreamSynchronize(s));
+    if (hist && nh > 0) PSK_HIP(hipMemcpy(hist, r.w.hist, (size_t)nh * 8, hipMemcpyDeviceToHost));
+    PSK_TRY(from_device_vec(r.w.x, loc, r.n, xout, r.s));
+    PSK_HIP(hipStreamSynchronize(r.s));
     return PSK_OK;
+}
+
+// the phases in order; the caller drains the stream when one fails
+static int bicg_solve(BicgRun &r, const double *b, double *xout, psk_result *res, double *hist, int32_t loc) {
+    PSK_TRY(bicg_workspace(r));
+    PSK_TRY(solve_kit(r.c, false, &r.kit));
+    StampPoll poll(r.kit);   // the host-mapped done stamp the kernels write (bicg_set_done)
+    bool run;
+    PSK_TRY(bicg_init(r, poll, b, loc, &run));
+    int64_t launched = 0;
+    for (int64_t k = 0; run && k < r.ctl->maxiter; ++k) {
+        bool stop;
+        PSK_TRY(poll.step<2>(k, r.C, r.s, &stop));
+        if (stop) break;
+        PSK_TRY(bicg_iteration(r, k));
+        launched = k + 1;
+    }
+    BicgState hs;
+    double true_sq;
+    PSK_TRY(bicg_finish(r, &hs, &true_sq, res));
+    return bicg_report(r, hs, launched, true_sq, res, hist, xout, loc);
 }
 
 }  // namespace psk
@@ -544,13 +580,11 @@ extern "C" int psk_bicgstab(const psk_csr *Ac, const psk_prec *M, const double *
     r.n = Ac->n;
     r.nv = r.n > 0 ? (r.n + kVecTile - 1) / kVecTile : 1;
     if (r.nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_bicgstab: vector too long for a one-shot grid");
+    r.C = ctl->check_every > 0 ? ctl->check_every : (r.n >= (1 << 20) ? 2 : 16);
     r.gen = prec_is_general(M);
     r.dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
     if (r.n == 0) {   // no rows: b = 0
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-        res->iters = 1;
-        res->exit = PSK_EXIT_NONE;
+        result_trivial(res);
         return PSK_OK;
     }
     const int rc = bicg_solve(r, b, xout, res, hist, loc);
@@ -558,3 +592,4 @@ extern "C" int psk_bicgstab(const psk_csr *Ac, const psk_prec *M, const double *
     if (rc != PSK_OK) (void)hipStreamSynchronize(r.s);
     return rc;
 }
+

@@ -482,7 +482,7 @@ static int gm_cycle_end(GmresRun &r, int64_t Kc, psk_result *res) {
     if (r.ctl->fail_on_maxiter) {
         res->status = PSK_MAXITER;
         res->success = 0;
-        std::snprintf(res->msg, sizeof(res->msg), "failure to converge");
+        result_msg(res, "failure to converge");
     } else {
         res->status = PSK_CONVERGED;
         res->success = 1;
@@ -500,9 +500,7 @@ static int gm_report(GmresRun &r, psk_result *res, double *hist, double *xout, i
     // as the error it is rather than as a numerical non-convergence (and never to a later solve)
     PSK_TRY(gridsum_check(r.c));
     if (r.gen) PSK_TRY(prec_check_error(r.M, r.s));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, r.kit->ev0, r.kit->ev1);
-    res->loop_ms = ms;
+    res->loop_ms = loop_ms(r.kit);
     res->norm_b = hs.normB;
     res->spmv_launches = r.spmvs;
     if (hs.zero_b) {   // b = 0: handleConvergence(0, zeros, 0, 0)
@@ -595,10 +593,7 @@ extern "C" int psk_gmres(const psk_csr *Ac, const psk_prec *M, const double *b, 
     r.dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
     PSK_TRY(gm_fits_hbm(r));
     if (r.n == 0) {   // no rows: b = 0
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-        res->iters = 1;
-        res->exit = PSK_EXIT_NONE;
+        result_trivial(res);
         return PSK_OK;
     }
     const int rc = gm_solve(r, b, xout, res, hist, loc);

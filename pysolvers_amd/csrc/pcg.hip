@@ -449,10 +449,6 @@ bool pcg_staggers(const psk_csr *A, const psk_prec *M) {
     return kPcgStagger > 0 && !prec_is_general(M) && !A->comm && A->n > 0 && spmv_flush_eligible(A);
 }
 
-static void set_msg(psk_result *res, const char *m) {
-    std::snprintf(res->msg, sizeof(res->msg), "%s", m);
-}
-
 // every path of a solve, decided once (pcg_plan); the phases read it
 struct PcgPlan {
     int64_t n, maxiter;
@@ -773,9 +769,7 @@ static int pcg_finish(PcgRun &r, PcgTimers &tm, PcgState *hs, psk_result *res) {
     PSK_TRY(gridsum_check_result(r.c, (int32_t)hw[kPcgStateWords]));
     if (r.pl.gen) PSK_TRY(prec_check_error(r.M, r.s));
     for (int i = 0; i < kTimedSlots; ++i) PSK_TRY(tm.harvest(i));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, kit->ev0, kit->ev1);
-    res->loop_ms = ms;
+    res->loop_ms = loop_ms(kit);
     return PSK_OK;
 }
 
@@ -801,7 +795,7 @@ static int pcg_report(const PcgState &hs, const PcgPlan &pl, int64_t launched, c
         res->success = 0;
         res->iters = hs.iters;
         res->resid = NAN;
-        set_msg(res, hs.brk_kind == 1 ? "breakdown dot(u,r)==0" : "breakdown dot(p, Ap)==0");
+        result_msg(res, hs.brk_kind == 1 ? "breakdown dot(u,r)==0" : "breakdown dot(p, Ap)==0");
         *nk = hs.brk_kind == 1 ? 0 : hs.iters + 1;
         nhist = hs.brk_kind == 1 ? 0 : hs.iters;
     } else {
@@ -810,7 +804,7 @@ static int pcg_report(const PcgState &hs, const PcgPlan &pl, int64_t launched, c
         res->exit = PSK_EXIT_MAXITER;
         res->success = 0;
         res->iters = maxiter > 0 ? maxiter - 1 : 0;
-        set_msg(res, "failure to converge");
+        result_msg(res, "failure to converge");
         *nk = nhist = launched;
     }
     // residual history (only when asked for), the recursive residual and the solution

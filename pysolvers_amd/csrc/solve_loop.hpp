@@ -1,8 +1,10 @@
 // solve_loop.hpp — host-side helpers of the device-loop solvers (psk_pcg, psk_bicgstab, psk_gmres, psk_vcycle): the
-// workspace carver and the done-stamp poll, both used by all four. Host code only: no kernel lives here (the
-// kernels' side of the stamp is done_stamp_store, psk_internal.hpp).
+// workspace carver, the done-stamp poll and the psk_result lines all four write alike. Host code only: no kernel
+// lives here (the kernels' side of the stamp is done_stamp_store, psk_internal.hpp).
 #pragma once
 #include "psk_internal.hpp"
+
+#include <cstdio>
 
 namespace psk {
 
@@ -25,7 +27,24 @@ struct Carve {
 void pcg_layout_probe(int64_t n, int64_t ncols, int64_t maxiter, bool gen, bool own_x, int P,
                       std::vector<int64_t> *log, int64_t *bytes);
 void gmres_layout_probe(int64_t n, int64_t maxiter, int64_t restart, bool gen, std::vector<int64_t> *log, int64_t *bytes);
+void bicgstab_layout_probe(int64_t n, int64_t maxiter, bool gen, std::vector<int64_t> *log, int64_t *bytes);
 void vcycle_layout_probe(int64_t n, int64_t maxiter, bool dev_io, std::vector<int64_t> *log, int64_t *bytes);
+
+// ---- what every solver writes into its psk_result the same way (res was zeroed by the entry point) ----
+inline void result_msg(psk_result *res, const char *m) { std::snprintf(res->msg, sizeof(res->msg), "%s", m); }
+// a solve with nothing to do (no rows, b = 0): x = 0, handleConvergence(0, zeros, 0, 0)
+inline void result_trivial(psk_result *res) {
+    res->status = PSK_CONVERGED;
+    res->success = 1;
+    res->iters = 1;
+    res->exit = PSK_EXIT_NONE;
+}
+// the interval between the solve's two events, both complete (0 when the runtime cannot tell)
+inline double loop_ms(const SolveKit *kit) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, kit->ev0, kit->ev1);
+    return ms;
+}
 
 // psk_gmres's workspace as the lab library reads it after a solve (gmres.hip gmres_work_view): device pointers
 // into the matrix's two buffers. Q: K + 1 columns of stride ldq doubles; H, R: (K + 1) x K column-major.

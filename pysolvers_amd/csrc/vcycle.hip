@@ -92,8 +92,6 @@ __global__ __launch_bounds__(kBlock) void vc_check_kernel(int64_t n, const doubl
     }
 }
 
-static void vc_msg(psk_result *res, const char *m) { std::snprintf(res->msg, sizeof(res->msg), "%s", m); }
-
 // the loop's device words: [state][hist maxiter][tickets], then b and the output when they are the host's. The
 // history follows the state unaligned: the final host copy reads both as one contiguous range.
 struct VcWork {
@@ -117,6 +115,135 @@ void vcycle_layout_probe(int64_t n, int64_t maxiter, bool dev_io, std::vector<in
     bytes[1] = 0;
 }
 
+// what the phases of one solve share
+struct VcRun {
+    const psk_prec *M;
+    const psk_ctl *ctl;
+    Context *c;
+    hipStream_t s;
+    int64_t n, maxiter;
+    bool dev_io;        // b and x are the caller's device vectors
+    int32_t flags;
+    AmgLoop lp;
+    VcWork w;
+    SolveKit *kit;
+    double *out;        // where vc_check_kernel snapshots x: the caller's device vector, or w.out
+    const double *bd;   // b on the device
+};
+
+static int vc_workspace(VcRun &r, double *xout) {
+    PSK_TRY(amg_loop_view(r.M, &r.lp));
+    int64_t need[2];
+    vcycle_layout_probe(r.n, r.maxiter, r.dev_io, nullptr, need);
+    PSK_TRY(r.lp.work->ensure((size_t)need[0]));
+    Carve cv{r.lp.work->as<char>()};
+    vc_layout(cv, r.n, r.maxiter, r.dev_io, r.w);
+    r.out = r.dev_io ? xout : r.w.out;
+    return PSK_OK;
+}
+
+// in front of the loop: b, ||b||^2 and x = copy(b) (or the caller's x), the state; the one wait, which tells
+// whether b = 0 (*zero_b: no cycle runs, :64-65)
+static int vc_init(VcRun &r, StampPoll &poll, const double *b, const double *xout, int32_t loc, bool *zero_b) {
+    hipStream_t s = r.s;
+    r.bd = b;
+    if (!r.dev_io) {
+        PSK_TRY(to_device_vec(b, loc, r.n, r.w.b, s));
+        r.bd = r.w.b;
+    }
+    PSK_HIP(hipEventRecord(r.kit->ev0, s));
+    PSK_TRY(amg_loop_start(r.M, r.c, r.bd, s));                                              // ||b||^2, x = copy(b)  :63, :69
+    if (r.flags & PSK_VCYCLE_X0_GIVEN) PSK_TRY(to_device_vec(xout, loc, r.n, r.lp.x, s));   // before `out` is written
+    PSK_HIP(hipMemsetAsync(r.w.tick, 0, kVcTickBytes, s));
+    hipLaunchKernelGGL(vc_init_kernel, dim3(1), dim3(1), 0, s, r.lp.normb2, r.w.st, poll.hdone(), poll.hgen());
+    PSK_HIP(hipGetLastError());
+    PSK_TRY(poll.wait(s));
+    *zero_b = poll.stamp() == 1;
+    return PSK_OK;
+}
+
+// cycle k, its residual and its check
+static int vc_iteration(VcRun &r, const StampPoll &poll, int64_t k) {
+    PSK_TRY(amg_cycle(r.M, r.c, r.bd, r.s));      // x = runCycle(b, x)  :81
+    PSK_TRY(amg_residual(r.M, r.bd, r.s));        // r = b - A x, ||r||^2 in the same launch  :84, :87
+    const dim3 gc((unsigned)((r.n + kBlock - 1) / kBlock));
+    hipLaunchKernelGGL(vc_check_kernel, gc, dim3(kBlock), 0, r.s, r.n, r.lp.x, r.out, r.lp.sum, r.ctl->tau, r.w.st, r.w.tick,
+                       r.w.hist, k, r.maxiter, poll.hdone(), poll.hgen());
+    PSK_HIP(hipGetLastError());
+    return PSK_OK;
+}
+
+// behind the loop: one copy for the state and the `launched` history entries (into host), the gridsum error word,
+// x; one synchronisation; then the two error checks and loop_ms
+static int vc_finish(VcRun &r, int64_t launched, bool zero_b, double *xout, int32_t loc, std::vector<double> &host,
+                     psk_result *res) {
+    hipStream_t s = r.s;
+    PSK_HIP(hipEventRecord(r.kit->ev1, s));
+    host.resize((size_t)(kVcStateWords + launched));
+    int32_t *gs_word = reinterpret_cast<int32_t *>(static_cast<char *>(r.kit->hstage) + kStageBytes - 64);
+    PSK_TRY(gridsum_check_enqueue(r.c, gs_word));
+    PSK_HIP(hipMemcpyAsync(host.data(), r.w.st, host.size() * 8, hipMemcpyDeviceToHost, s));
+    if (zero_b) PSK_HIP(hipMemsetAsync(r.out, 0, (size_t)r.n * 8, s));   // np.zeros_like(b)  :65
+    if (!r.dev_io) PSK_TRY(from_device_vec(r.out, loc, r.n, xout, s));
+    PSK_HIP(hipStreamSynchronize(s));
+    PSK_TRY(gridsum_check_result(r.c, *gs_word));
+    PSK_TRY(prec_check_error(r.M, s));
+    res->loop_ms = loop_ms(r.kit);
+    return PSK_OK;
+}
+
+// host = [state][history] of a loop that enqueued `launched` cycles, decoded into res and hist
+static int vc_report(const VcRun &r, int64_t launched, bool zero_b, const std::vector<double> &host, psk_result *res,
+                     double *hist) {
+    VcState hs;
+    std::memcpy(&hs, host.data(), sizeof(VcState));
+    res->norm_b = hs.normB;
+    res->spmv_launches = launched;
+    if (zero_b) {                       // handleConvergence(0, zeros, 0, 0)
+        result_trivial(res);
+        return PSK_OK;
+    }
+    const int64_t nh = hs.nhist < launched ? hs.nhist : launched;
+    res->hist_len = nh;
+    res->resid = res->resid_recursive = hs.resid;
+    if (hist && nh > 0) std::memcpy(hist, host.data() + kVcStateWords, (size_t)nh * 8);
+    if (hs.conv_iter >= 0) {            // handleConvergence(k, x, normR, normB)  :91
+        res->status = PSK_CONVERGED;
+        res->success = 1;
+        res->iters = hs.conv_iter + 1;
+        res->exit = PSK_EXIT_TOLERANCE;
+    } else {                            // handleMaxiter(maxiter - 1, x, normR, normB)  :95
+        if (launched != r.maxiter) return fail(PSK_ERR_HIP, "psk_vcycle: the loop stopped without a converged cycle");
+        res->status = PSK_MAXITER;
+        res->success = r.ctl->fail_on_maxiter ? 0 : 1;
+        res->iters = r.maxiter - 1;
+        res->exit = PSK_EXIT_MAXITER;
+        if (r.ctl->fail_on_maxiter) result_msg(res, "failure to converge");
+    }
+    return PSK_OK;
+}
+
+// the phases in order; the caller drains the stream when one fails
+static int vc_solve(VcRun &r, const double *b, double *xout, psk_result *res, double *hist, int32_t loc) {
+    PSK_TRY(vc_workspace(r, xout));
+    PSK_TRY(solve_kit(r.c, false, &r.kit));
+    StampPoll poll(r.kit);   // the host-mapped done stamp vc_init_kernel and vc_check_kernel write
+    bool zero_b;
+    PSK_TRY(vc_init(r, poll, b, xout, loc, &zero_b));
+    const int C = r.ctl->check_every > 0 ? r.ctl->check_every : 1;
+    int64_t launched = 0;
+    for (int64_t k = 0; k < r.maxiter && !zero_b; ++k) {
+        bool stop;
+        PSK_TRY(poll.step<kVcLag>(k, C, r.s, &stop));
+        if (stop) break;
+        PSK_TRY(vc_iteration(r, poll, k));
+        launched = k + 1;
+    }
+    std::vector<double> host;
+    PSK_TRY(vc_finish(r, launched, zero_b, xout, loc, host, res));
+    return vc_report(r, launched, zero_b, host, res, hist);
+}
+
 }  // namespace psk
 
 using namespace psk;
@@ -128,111 +255,24 @@ extern "C" int psk_vcycle(const psk_prec *M, const double *b, double *xout, cons
     if (ctl->maxiter <= 0) return fail(PSK_ERR_ARG, "psk_vcycle: maxiter <= 0");   // the reference: NameError (:95)
     if (flags & ~PSK_VCYCLE_X0_GIVEN) return fail(PSK_ERR_ARG, "psk_vcycle: unknown flags");
     if (loc != PSK_HOST && loc != PSK_DEVICE) return fail(PSK_ERR_ARG, "psk_vcycle: bad loc");
-    Context *c;
-    PSK_TRY(ctx(&c));
-    std::lock_guard<std::mutex> solve_lock(c->solve_mu);
-    hipStream_t s = c->stream;
+    VcRun r{};
+    r.M = M;
+    r.ctl = ctl;
+    PSK_TRY(ctx(&r.c));
+    std::lock_guard<std::mutex> solve_lock(r.c->solve_mu);
+    r.s = r.c->stream;
     std::memset(res, 0, sizeof(*res));
-    const int64_t n = M->n, maxiter = ctl->maxiter;
-    if (n == 0) {   // ||b|| = 0
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-        res->iters = 1;
-        res->exit = PSK_EXIT_NONE;
+    r.n = M->n;
+    r.maxiter = ctl->maxiter;
+    r.dev_io = loc == PSK_DEVICE;
+    r.flags = flags;
+    if (r.n == 0) {   // ||b|| = 0
+        result_trivial(res);
         return PSK_OK;
     }
-    AmgLoop lp;
-    PSK_TRY(amg_loop_view(M, &lp));
-    const bool dev_io = loc == PSK_DEVICE;
-    int64_t need[2];
-    vcycle_layout_probe(n, maxiter, dev_io, nullptr, need);
-    PSK_TRY(lp.work->ensure((size_t)need[0]));
-    Carve cv{lp.work->as<char>()};
-    VcWork w;
-    vc_layout(cv, n, maxiter, dev_io, w);
-    VcState *st = w.st;
-    double *dhist = w.hist, *out = dev_io ? xout : w.out;
-    uint32_t *tick = w.tick;
-    SolveKit *kit;
-    PSK_TRY(solve_kit(c, false, &kit));
-    StampPoll poll(kit);
-
-    int rc = PSK_OK;
-    auto body = [&]() -> int {
-        const double *bd = b;
-        if (!dev_io) {
-            PSK_TRY(to_device_vec(b, loc, n, w.b, s));
-            bd = w.b;
-        }
-        PSK_HIP(hipEventRecord(kit->ev0, s));
-        PSK_TRY(amg_loop_start(M, c, bd, s));                                            // ||b||^2, x = copy(b)  :63, :69
-        if (flags & PSK_VCYCLE_X0_GIVEN) PSK_TRY(to_device_vec(xout, loc, n, lp.x, s));   // before `out` is written
-        PSK_HIP(hipMemsetAsync(tick, 0, kVcTickBytes, s));
-        hipLaunchKernelGGL(vc_init_kernel, dim3(1), dim3(1), 0, s, lp.normb2, st, poll.hdone(), poll.hgen());
-        PSK_HIP(hipGetLastError());
-        // the one wait in front of the loop: b = 0 runs no cycle (:64-65)
-        PSK_TRY(poll.wait(s));
-        const bool zero_b = poll.stamp() == 1;
-        const int C = ctl->check_every > 0 ? ctl->check_every : 1;
-        const dim3 gc((unsigned)((n + kBlock - 1) / kBlock));
-        int64_t launched = 0;
-        for (int64_t k = 0; k < maxiter && !zero_b; ++k) {
-            bool stop;
-            PSK_TRY(poll.step<kVcLag>(k, C, s, &stop));
-            if (stop) break;
-            PSK_TRY(amg_cycle(M, c, bd, s));      // x = runCycle(b, x)  :81
-            PSK_TRY(amg_residual(M, bd, s));      // r = b - A x, ||r||^2 in the same launch  :84, :87
-            hipLaunchKernelGGL(vc_check_kernel, gc, dim3(kBlock), 0, s, n, lp.x, out, lp.sum, ctl->tau, st, tick, dhist, k,
-                               maxiter, poll.hdone(), poll.hgen());
-            PSK_HIP(hipGetLastError());
-            launched = k + 1;
-        }
-        PSK_HIP(hipEventRecord(kit->ev1, s));
-        // one copy for the state and the history, the gridsum error word, x; one synchronisation
-        std::vector<double> host((size_t)(kVcStateWords + launched));
-        int32_t *gs_word = reinterpret_cast<int32_t *>(static_cast<char *>(kit->hstage) + kStageBytes - 64);
-        PSK_TRY(gridsum_check_enqueue(c, gs_word));
-        PSK_HIP(hipMemcpyAsync(host.data(), st, host.size() * 8, hipMemcpyDeviceToHost, s));
-        if (zero_b) PSK_HIP(hipMemsetAsync(out, 0, (size_t)n * 8, s));   // np.zeros_like(b)  :65
-        if (!dev_io) PSK_TRY(from_device_vec(out, loc, n, xout, s));
-        PSK_HIP(hipStreamSynchronize(s));
-        PSK_TRY(gridsum_check_result(c, *gs_word));
-        PSK_TRY(prec_check_error(M, s));
-        VcState hs;
-        std::memcpy(&hs, host.data(), sizeof(VcState));
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, kit->ev0, kit->ev1);
-        res->loop_ms = ms;
-        res->norm_b = hs.normB;
-        res->spmv_launches = launched;
-        if (zero_b) {                       // handleConvergence(0, zeros, 0, 0)
-            res->status = PSK_CONVERGED;
-            res->success = 1;
-            res->iters = 1;
-            res->exit = PSK_EXIT_NONE;
-            return PSK_OK;
-        }
-        const int64_t nh = hs.nhist < launched ? hs.nhist : launched;
-        res->hist_len = nh;
-        res->resid = res->resid_recursive = hs.resid;
-        if (hist && nh > 0) std::memcpy(hist, host.data() + kVcStateWords, (size_t)nh * 8);
-        if (hs.conv_iter >= 0) {            // handleConvergence(k, x, normR, normB)  :91
-            res->status = PSK_CONVERGED;
-            res->success = 1;
-            res->iters = hs.conv_iter + 1;
-            res->exit = PSK_EXIT_TOLERANCE;
-        } else {                            // handleMaxiter(maxiter - 1, x, normR, normB)  :95
-            if (launched != maxiter) return fail(PSK_ERR_HIP, "psk_vcycle: the loop stopped without a converged cycle");
-            res->status = PSK_MAXITER;
-            res->success = ctl->fail_on_maxiter ? 0 : 1;
-            res->iters = maxiter - 1;
-            res->exit = PSK_EXIT_MAXITER;
-            if (ctl->fail_on_maxiter) vc_msg(res, "failure to converge");
-        }
-        return PSK_OK;
-    };
-    rc = body();
+    const int rc = vc_solve(r, b, xout, res, hist, loc);
     // a solve that failed on the host side leaves no kernel of its own running behind the next solve
-    if (rc != PSK_OK) (void)hipStreamSynchronize(s);
+    if (rc != PSK_OK) (void)hipStreamSynchronize(r.s);
     return rc;
 }
+

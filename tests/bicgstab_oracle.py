@@ -50,16 +50,17 @@ def identity(v):
 
 
 def bicgstab(A, b, M=identity, maxiter=100, tau=1.0e-8, fail_on_maxiter=True, dot=dot_numpy, norm_b=0.0):
-    """dict(status, success, iters, exit, hist, soln, resid, norm_b, msg) in the conventions of psk_result as the
-    Python layer reports them: converged at k -> iters = k + 1; breakdown at k -> iters = k; maxiter ->
-    iters = maxiter - 1. resid: the true ||b - A x|| on a tolerance exit, else the last recursive one."""
+    """dict(status, success, iters, exit, half, hist, soln, resid, norm_b, msg) in the conventions of psk_result as
+    the Python layer reports them: converged at k -> iters = k + 1; breakdown at k -> iters = k; maxiter ->
+    iters = maxiter - 1. resid: the true ||b - A x|| on a tolerance exit, else the last recursive one. half: the
+    tolerance exit was the half step's (||s||), which runs one SpMV of its iteration, not two."""
     b = np.asarray(b, dtype=np.float64)
     n = len(b)
     x = np.zeros(n)
     bb = dot(b, b)
     normB = float(norm_b) if norm_b > 0 else math.sqrt(bb)
-    out = dict(status="converged", success=True, iters=1, exit="none", hist=np.zeros(0), soln=x, resid=0.0,
-               norm_b=normB, msg=None)
+    out = dict(status="converged", success=True, iters=1, exit="none", half=False, hist=np.zeros(0), soln=x,
+               resid=0.0, norm_b=normB, msg=None)
     if bb == 0.0:
         return out
     thresh = tau * normB
@@ -76,11 +77,11 @@ def bicgstab(A, b, M=identity, maxiter=100, tau=1.0e-8, fail_on_maxiter=True, do
         return done(status="breakdown", success=False, iters=k, exit="breakdown", soln=None, resid=float("nan"),
                     msg="breakdown " + what)
 
-    def tolerance_exit(k, x):
+    def tolerance_exit(k, x, half=False):
         tr = float(np.linalg.norm(b - krylov.mvmult(A, x)))
         ok = tr <= thresh
         return done(status="converged" if ok else "true residual above tolerance", success=ok, iters=k + 1,
-                    exit="tolerance", soln=x, resid=tr)
+                    exit="tolerance", half=half, soln=x, resid=tr)
 
     for k in range(maxiter):
         ph = M(p)
@@ -94,7 +95,7 @@ def bicgstab(A, b, M=identity, maxiter=100, tau=1.0e-8, fail_on_maxiter=True, do
         if ns <= thresh:
             x = x + alpha * ph
             hist.append(ns)
-            return tolerance_exit(k, x)
+            return tolerance_exit(k, x, half=True)
         sh = M(s)
         t = krylov.mvmult(A, sh)
         ts = dot(t, s)

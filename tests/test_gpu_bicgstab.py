@@ -151,7 +151,20 @@ def test_prefix_parity_with_the_oracle(psk, name):
     _check_prefix_parity(name, st)
     assert st.info["status"] == "converged" and len(st.info["hist"]) == st.iters()
     assert st.resid() <= TAU * st.info["norm_b"]                     # the true residual the device measured
-    assert st.info["spmv_launches"] in (2 * st.iters(), 2 * st.iters() + 1)   # 2 per iteration (1 in a half step) + 1
+    # 2 SpMV launches per iteration, 1 in the iteration a half-step exit ends, + 1 for the true residual. Which
+    # exit the device took: with tau = 0 the same iterations run (tau only stops them) and the last one takes its
+    # full step, so its history entry is ||r||; the solve's own last entry is that, or the half step's ||s||.
+    # Where the oracle's three dot orders agree on the count they also say which exit it is.
+    k = st.iters() - 1
+    full = _raw(_system(psk, name), _rhs(name), maxiter=k + 1, tau=0.0)[1]
+    assert np.array_equal(_bits(full[:k]), _bits(st.info["hist"][:k]))
+    half = _bits(full)[k] != _bits(st.info["hist"])[k]
+    res, _ = _reference(name)
+    if bo.counts_comparable(res, TAU):
+        assert {r["half"] for r in res} == {half}, (name, half)
+    print("%s: %s tolerance exit at k = %d, %d SpMV launches" % (name, "half-step" if half else "full-step", k,
+                                                                st.info["spmv_launches"]))
+    assert st.info["spmv_launches"] == 2 * st.iters() + (0 if half else 1)
 
 
 @pytest.mark.parametrize("name", ["cd17", "cd33", "cd64"])
@@ -251,6 +264,120 @@ def test_tau_zero_runs_to_maxiter_with_a_finite_history(psk):
     h = st.info["hist"]
     assert len(h) == 30 and np.all(np.isfinite(h))
     assert st.info["spmv_launches"] == 60
+
+
+# ---- psk_bicgstab itself: the whole psk_result per exit kind, the stamp's generation, check_every ------------------
+# (past the Python layer, which answers b = 0 before it calls the library and always passes check_every = 0)
+
+INT_FIELDS = ("status", "success", "exit", "iters", "hist_len", "spmv_launches", "comm_samples")
+_systems = {}
+
+
+def _system(psk, name, prec=None):
+    """(DeviceCSR, formed preconditioner or None for the identity) of a case, built once."""
+    prec = CASES[name] if prec is None else prec
+    if (name, prec) not in _systems:
+        dA = psk.DeviceCSR.from_scipy(_matrix(name))
+        _systems[name, prec] = (dA, None if prec == "identity" else _device_prec(psk, name).form(dA))
+    return _systems[name, prec]
+
+
+def _raw(system, b, **kw):
+    """One psk_bicgstab call on host vectors: (x, hist, result)."""
+    import ctypes
+    from pysolvers_amd import _native as N
+    dA, M = system
+    kw.setdefault("maxiter", MAXITER)
+    kw.setdefault("tau", TAU)
+    kw.setdefault("fail_on_maxiter", 1)
+    ctl = N.PskCtl(restart=0, time_kernels=0, norm_b=0.0, **kw)
+    res = N.PskResult()
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    x = np.full(b.size, np.nan)
+    hist = np.zeros(ctl.maxiter + 1)
+    N.check(N.lib.psk_bicgstab(dA.handle, M.device_handle if M is not None else None, N.ptr(b), N.ptr(x),
+                               ctypes.byref(ctl), ctypes.byref(res), N.ptr(hist), N.PSK_HOST), "psk_bicgstab")
+    return x, hist[:res.hist_len].copy(), res
+
+
+def _same(a, b, tag):
+    (xa, ha, ra), (xb, hb, rb) = a, b
+    assert xa.tobytes() == xb.tobytes(), tag
+    assert ha.tobytes() == hb.tobytes(), tag
+    assert [getattr(ra, f) for f in INT_FIELDS] == [getattr(rb, f) for f in INT_FIELDS], tag
+    for f in ("resid", "resid_recursive", "norm_b"):
+        assert np.float64(getattr(ra, f)).tobytes() == np.float64(getattr(rb, f)).tobytes(), (tag, f)
+    assert ra.msg == rb.msg, tag
+
+
+@pytest.mark.parametrize("kind", ["rhatv_breakdown", "maxiter_fail", "maxiter_no_fail", "zero_b_jacobi",
+                                  "zero_b_general"])
+def test_whole_result_per_exit_kind(psk, kind):
+    """status, success, exit, iters, hist_len, spmv_launches, resid, resid_recursive of every exit that is not a
+    tolerance exit (those: test_prefix_parity_with_the_oracle, test_diagonal_matrix_takes_the_half_step_exit).
+    spmv_launches counts the SpMV launches that did their work: 2 per completed iteration, 1 in an iteration the
+    rhat.v test ended, none behind `done`, and no true-residual launch except on a tolerance exit."""
+    from pysolvers_amd import _native as N
+    mi = 5
+    if kind == "rhatv_breakdown":
+        dA = psk.DeviceCSR.from_scipy(sp.csr_matrix(np.array([[0.0, 1.0], [-1.0, 0.0]])))
+        x, h, r = _raw((dA, None), np.array([1.0, 0.0]))
+        want = (N.PSK_BREAKDOWN, 0, N.PSK_EXIT_DOT_BREAKDOWN, 0, 0, 1, 0)
+        assert np.isnan(r.resid) and r.resid_recursive == r.norm_b == 1.0   # no residual was reported: ||b||
+        assert r.msg == b"breakdown dot(rhat,v)==0"
+    elif kind.startswith("maxiter"):
+        fail = kind == "maxiter_fail"
+        x, h, r = _raw(_system(psk, "cd17"), _rhs("cd17"), maxiter=mi, fail_on_maxiter=int(fail))
+        want = (N.PSK_MAXITER, 0, N.PSK_EXIT_MAXITER, mi - 1, mi, 2 * mi, 0) if fail else \
+            (N.PSK_CONVERGED, 1, N.PSK_EXIT_MAXITER, mi, mi, 2 * mi, 0)
+        assert h[-1] > TAU * r.norm_b                        # not a tolerance exit: no true residual is measured
+        assert r.resid == h[-1] and r.resid_recursive == h[-1]
+        assert r.msg == (b"failure to converge" if fail else b"")
+        assert np.all(np.isfinite(x))
+    else:
+        name = "cd17" if kind == "zero_b_jacobi" else "fd17_cheb"
+        x, h, r = _raw(_system(psk, name), np.zeros(_matrix(name).shape[0]))
+        want = (N.PSK_CONVERGED, 1, N.PSK_EXIT_NONE, 1, 0, 0, 0)
+        assert r.resid == 0.0 and r.resid_recursive == 0.0 and r.norm_b == 0.0
+        assert not np.any(x) and r.msg == b""
+    assert tuple(getattr(r, f) for f in INT_FIELDS) == want, (kind, [getattr(r, f) for f in INT_FIELDS])
+    assert len(h) == r.hist_len
+    assert (r.spmv_ms, r.gather_ms, r.halo_ms) == (0.0, 0.0, 0.0)
+
+
+@pytest.mark.parametrize("name", ["cd17", "fd17_cheb"])
+def test_a_zero_solve_leaves_no_stamp_behind(psk, name):
+    """The done stamp of a b = 0 solve (1, tagged with that solve's generation) is not one the next solve acts
+    on: the same solve directly after a b = 0 solve gives the bits it gave before. Jacobi, and a general
+    preconditioner (whose solve reads the stamp in front of its loop)."""
+    from pysolvers_amd import _native as N
+    system, b = _system(psk, name), _rhs(name)
+    first = _raw(system, b)
+    assert first[2].status == N.PSK_CONVERGED and first[2].exit == N.PSK_EXIT_TOLERANCE and first[2].iters > 1
+    zero = _raw(system, np.zeros(b.size))
+    assert zero[2].exit == N.PSK_EXIT_NONE and zero[2].spmv_launches == 0
+    _same(first, _raw(system, b), name)
+
+
+@pytest.mark.parametrize("stop", ["tolerance", "maxiter10"])
+@pytest.mark.parametrize("name,prec", [("cd17", "jacobi"), ("rand513", "identity")])
+def test_check_every_never_shows(psk, name, prec, stop):
+    """The poll chunk (ctl.check_every: 1, 3, and 16 > maxiter = 10) shows in nothing: x, the history and every
+    integer field of the result, spmv_launches included (it counts launches that did their work, not enqueued
+    ones). tests/test_gpu_solve_loop.py holds psk_pcg to the same."""
+    from pysolvers_amd import _native as N
+    system, b = _system(psk, name, prec), _rhs(name)
+    kw = {} if stop == "tolerance" else dict(maxiter=10)
+    runs = [_raw(system, b, check_every=C, **kw) for C in (1, 3, 16)]
+    r0 = runs[0][2]
+    if stop == "tolerance":
+        assert (r0.status, r0.success, r0.exit) == (N.PSK_CONVERGED, 1, N.PSK_EXIT_TOLERANCE)
+        assert 10 < r0.iters < MAXITER and r0.hist_len == r0.iters
+    else:
+        assert (r0.status, r0.success, r0.exit) == (N.PSK_MAXITER, 0, N.PSK_EXIT_MAXITER)
+        assert r0.iters == 9 and r0.hist_len == 10 and r0.spmv_launches == 20
+    for i, run in enumerate(runs[1:]):
+        _same(runs[0], run, (name, prec, stop, i + 1))
 
 
 # ---- determinism ---------------------------------------------------------------------------------------------------

@@ -210,6 +210,81 @@ def test_zero_rhs_in_the_library(psk, fix):
                             N.PSK_HOST) == N.PSK_ERR_ARG
 
 
+# ---- psk_vcycle's host loop: check_every, the number of cycles enqueued, the stamp's generation ----------------
+VC_LAG = 1   # kVcLag (vcycle.hip): the poll reads the stamp behind the event VC_LAG chunks back
+
+
+def _raw(M, b, maxiter=60, check_every=0):
+    """One psk_vcycle call on host vectors, tau = 1e-10: (x, hist, result)."""
+    from pysolvers_amd import _native as N
+    ctl = N.PskCtl(maxiter=maxiter, tau=1e-10, fail_on_maxiter=1, restart=0, check_every=check_every, time_kernels=0,
+                   norm_b=0.0)
+    res, x, hist = N.PskResult(), np.full(b.size, 7.0), np.zeros(maxiter)
+    N.check(N.lib.psk_vcycle(M.device_handle, N.ptr(b), N.ptr(x), ctypes.byref(ctl), ctypes.byref(res), N.ptr(hist),
+                             0, N.PSK_HOST), "psk_vcycle")
+    return x, hist[:res.hist_len].copy(), res
+
+
+def _cycles_enqueued(c, C, maxiter):
+    """res.spmv_launches of a solve whose cycle c converged, polled in chunks of C cycles (StampPoll::step): in
+    front of cycle k = j C the host waits for the event behind chunk j - 1 - VC_LAG, which covers the cycles below
+    (j - VC_LAG) C, and stops when the stamp c + 2 is at most (j - VC_LAG) C + 1. So k is the least j C with
+    j >= VC_LAG + 1 and c + 2 <= (j - VC_LAG) C + 1, and never more than maxiter."""
+    j = VC_LAG + 1
+    while c + 2 > (j - VC_LAG) * C + 1:
+        j += 1
+    return min(j * C, maxiter)
+
+
+def _same(a, b, tag):
+    (xa, ha, ra), (xb, hb, rb) = a, b
+    assert np.array_equal(_bits(xa), _bits(xb)), tag
+    assert np.array_equal(_bits(ha), _bits(hb)), tag
+    assert (ra.iters, ra.status, ra.exit, ra.success, ra.hist_len) == (rb.iters, rb.status, rb.exit, rb.success,
+                                                                       rb.hist_len), tag
+    assert _bits(np.float64(ra.resid)) == _bits(np.float64(rb.resid)), tag
+
+
+@pytest.mark.parametrize("what,L", [("fd128", 3), ("tri145", 2)])
+def test_check_every_shows_only_in_the_cycles_enqueued(psk, fd128, what, L):
+    from pysolvers_amd import _native as N
+    from pysolvers_amd.Linear import AMGPreconditioner
+    if what == "fd128":
+        A, b, ref = fd128
+    else:
+        A, b, ref = _tridiag(145), np.random.default_rng(145).standard_normal(145), None
+    M = AMGPreconditioner(A, numIters=1, numLevels=L, tau=0.0)
+    runs = {C: _raw(M, b, check_every=C) for C in (1, 2, 5)}
+    r1 = runs[1][2]
+    assert (r1.status, r1.success, r1.exit) == (N.PSK_CONVERGED, 1, N.PSK_EXIT_TOLERANCE)
+    assert 2 <= r1.iters < 60 and r1.hist_len == r1.iters and (ref is None or r1.iters == ref["iters"])
+    for C in (1, 2, 5):
+        _same(runs[1], runs[C], (what, C))
+        got, want = runs[C][2].spmv_launches, _cycles_enqueued(r1.iters - 1, C, 60)
+        print("%s check_every %d: cycle %d converged, %d enqueued (rule %d)" % (what, C, r1.iters - 1, got, want))
+        assert got == want, (what, C, got, want)
+    # the cap: maxiter = the converging cycle + 2, below what a chunk of 5 would enqueue
+    capped = _raw(M, b, maxiter=r1.iters + 1, check_every=5)
+    _same(runs[1], capped, (what, "capped"))
+    assert capped[2].spmv_launches == _cycles_enqueued(r1.iters - 1, 5, r1.iters + 1) == r1.iters + 1
+
+
+def test_a_zero_solve_leaves_no_stamp_behind(psk, fd128):
+    """b = 0 stores the stamp 1 under its own generation: the fd128 solve directly after it gives the bits it gave
+    before, and enqueues the same number of cycles."""
+    from pysolvers_amd import _native as N
+    from pysolvers_amd.Linear import AMGPreconditioner
+    A, b, ref = fd128
+    M = AMGPreconditioner(A, numIters=1, numLevels=3, tau=0.0)
+    first = _raw(M, b)
+    assert first[2].iters == ref["iters"] and first[2].exit == N.PSK_EXIT_TOLERANCE
+    zero = _raw(M, np.zeros(b.size))
+    assert (zero[2].exit, zero[2].iters, zero[2].spmv_launches) == (N.PSK_EXIT_NONE, 1, 0) and not np.any(zero[0])
+    after = _raw(M, b)
+    _same(first, after, "after b = 0")
+    assert after[2].spmv_launches == first[2].spmv_launches
+
+
 def test_maxiter_one(psk, fix):
     from vcycle_oracle import vcycle_solve
     A, b = _matrix(fix, "negfd16"), fix["negfd16_b"]

@@ -1,4 +1,4 @@
-"""The workspace layouts of psk_pcg, psk_gmres and psk_vcycle (solve_loop.hpp Carve, through psk_lab_solver_layout;
+"""The workspace layouts of psk_pcg, psk_gmres, psk_bicgstab and psk_vcycle (solve_loop.hpp Carve, through psk_lab_solver_layout;
 no GPU). Each solver sizes its buffers and carves its pointers with one layout function; here every offset is
 recomputed from the formulas the solvers used before that (one chain of 256-byte-rounded terms for the size, a
 second one for the pointers), written out independently.
@@ -14,11 +14,12 @@ import pytest
 
 from pysolvers_amd import _native as N
 
-PCG, GMRES, VCYCLE = 0, 1, 2
+PCG, GMRES, VCYCLE, BICGSTAB = 0, 1, 2, 3
 GEN, OWN_X, DEV_IO = 1, 2, 4
 MAX_GRID = 2048          # kMaxGrid
 STATE = 256              # sizeof(PcgState) (80) and sizeof(GmresState) (64) rounded up to 256
 VC_STATE = 64            # sizeof(VcState)
+BICG_STATE = 112         # sizeof(BicgState): 6 int32, 2 int64, 7 doubles, a pointer, an int64
 VC_TICK = 65 * 64 * 4    # (kVcGroups + 1) counters, one per 256-byte line
 
 
@@ -135,10 +136,27 @@ def test_vcycle_layout(dev_io):
         check(offs, ext, size[0], unaligned=(1,))
 
 
+@pytest.mark.parametrize("gen", (0, 1))
+def test_bicgstab_layout(gen):
+    for n, maxiter in itertools.product((0, 1, 511, 512, 513), (0, 1, 100)):
+        offs, size = layout(BICGSTAB, n=n, maxiter=maxiter, flags=gen * GEN)
+        # the large workspace: bv, x, r, p, v, s, t, then ph and sh for a general preconditioner
+        vec, nbig = up(n * 8), 9 if gen else 7
+        want = [i * vec for i in range(nbig)]
+        assert offs[:nbig] == want, (n, maxiter, offs, want)
+        assert size[0] == (nbig * vec if n > 0 else 256)
+        check(offs[:nbig], [n * 8] * nbig, size[0])
+        # the small one: the state, the 8 sums, the history (one entry more than maxiter)
+        ext = [BICG_STATE, 64, (maxiter + 1) * 8]
+        assert offs[nbig:] == [0, 256, 512], (n, maxiter, offs[nbig:])
+        assert size[1] == 512 + up((maxiter + 1) * 8)
+        check(offs[nbig:], ext, size[1])
+
+
 def test_rejects_bad_arguments():
     lab = N.load_lab()
     off, cnt, nbytes = (N.I64 * 64)(), N.I32(64), (N.I64 * 2)()
-    assert lab.psk_lab_solver_layout(3, 1, 1, 1, 0, 0, 1, off, ctypes.byref(cnt), nbytes) != 0
+    assert lab.psk_lab_solver_layout(4, 1, 1, 1, 0, 0, 1, off, ctypes.byref(cnt), nbytes) != 0
     assert lab.psk_lab_solver_layout(PCG, -1, 1, 1, 0, 0, 1, off, ctypes.byref(cnt), nbytes) != 0
     assert lab.psk_lab_solver_layout(PCG, 1, 1, 1, 0, 0, 0, off, ctypes.byref(cnt), nbytes) != 0
     cnt = N.I32(2)
