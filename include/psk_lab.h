@@ -37,6 +37,17 @@ int psk_lab_trisolve_workers(const psk_prec *M, int32_t which, int32_t *enrolled
 int psk_lab_trisolve_plan(int64_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, int32_t upper,
                           int32_t unit, const int32_t *nat, int32_t num_cus, int64_t syncfree_waves, int32_t *schedule,
                           double *est, int64_t *info);
+/* Lab / tests of the host shard planner (dist_plan and dist_peers, dist_plan.hip); touches no GPU. The plan
+ * psk_csr_create_dist makes for rank `rank` of P: rows [row_starts[rank], row_starts[rank+1]) of a global CSR with
+ * n_global columns, given as that block's rowptr (nloc + 1 entries, any base) and colidx (global columns).
+ * row_starts and rowptr must be monotone (psk_csr_create_dist checks that before it plans). Outputs, all allocated
+ * by the caller: lcol[nnz] = the local column of every entry; halo = the global ids of the halo columns, *nhalo of
+ * them (at most nnz); pack = the send rows of the packed peers, concatenated, *npack of them (at most nnz);
+ * peers[7 * k ..] = rank, send_count, send_begin, packed, pack_off, recv_count, recv_offset of halo peer k, *npeers
+ * of them (at most P). A column index outside [0, n_global) is refused with PSK_ERR_ARG. */
+int psk_lab_dist_plan(int64_t n_global, const int64_t *row_starts, int32_t P, int32_t rank, const int64_t *rowptr,
+                      const int32_t *colidx, int32_t *lcol, int64_t *halo, int64_t *nhalo, int32_t *pack, int64_t *npack,
+                      int64_t *peers, int32_t *npeers);
 /* Lab / tests of the AMG smoother's paired Gauss-Seidel sweeps (round 6, amg_gs_pair.hip gs_pair_kernel): set = 0
  * runs every level's sweeps one launch each (the serialized path), 1 pairs them on the levels that qualify, -1
  * leaves the setting; *levels_on = the levels pairing now, *levels_eligible = the levels that qualify. */

@@ -32,7 +32,7 @@ def local_block(m, plan, a=-1.0, b=1.0):
 
 
 def _allreduce(dist, vals):
-    """Sum over ranks the way libpsk does it (dist.hip allgather): gather every rank's values, then
+    """Sum over ranks the way libpsk does it (dist_halo.hip allgather): gather every rank's values, then
     add them in rank order on every rank, so all ranks hold the same bits."""
     import torch
     t = torch.tensor(vals, dtype=torch.float64)
@@ -74,7 +74,7 @@ def dist_pcg(dist, m, Aloc, b, plan, maxiter, tau, fail_on_maxiter=True, jacobi=
 
 
 def shard_plan(A, row_starts, rank):
-    """General row-block plan of psk_csr_create_dist (pysolvers_amd/csrc/dist.hip dist_plan):
+    """General row-block plan of psk_csr_create_dist (pysolvers_amd/csrc/dist_plan.hip dist_plan):
     local columns [owned | halo] with the halo = distinct off-block columns ascending; receive
     from q = the halo segment q owns; send to q = the owned rows with an entry in q's block
     (== what q receives from us when the pattern is structurally symmetric)."""

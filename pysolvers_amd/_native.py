@@ -128,6 +128,8 @@ LAB_SIGNATURES = {
     "psk_lab_trisolve_workers": (ctypes.c_int, [P, I32, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
     "psk_lab_trisolve_plan": (ctypes.c_int, [I64, P, P, P, I32, I32, P, I32, I64, ctypes.POINTER(I32),
                                              ctypes.POINTER(F64), ctypes.POINTER(I64)]),
+    "psk_lab_dist_plan": (ctypes.c_int, [I64, P, I32, I32, P, P, P, P, ctypes.POINTER(I64), P, ctypes.POINTER(I64), P,
+                                         ctypes.POINTER(I32)]),
     "psk_lab_amg_gs_pair": (ctypes.c_int, [P, I32, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
     "psk_lab_spmv_rotate": (ctypes.c_int, [P, ctypes.POINTER(P), ctypes.POINTER(P), I32, I32, I32, ctypes.POINTER(F64)]),
     "psk_lab_cheby_ab": (ctypes.c_int, [P, P, I32, ctypes.POINTER(F64), ctypes.POINTER(F64)]),

@@ -31,6 +31,7 @@
 // the half-step exit's x += alpha ph (one small launch, only then), and on a tolerance exit one kSpmvResid
 // launch for the true residual ||b - A x||.
 #include "psk_internal.hpp"
+#include "dist.hpp"
 #include "solve_loop.hpp"
 
 #include <cmath>

@@ -255,10 +255,7 @@ int cheby_ab(const psk_prec *M, const double *v, int reps, double *fused_ms, dou
     const TileMap tm = tile_map_chunked(nt, kChebyChunk);
     const double al = ch->coef[1], be = ch->coef[2];
     DevBuf tmp;
-    struct Release {
-        DevBuf &b;
-        ~Release() { b.release(); }
-    } rel{tmp};
+    DevBufRelease rel{tmp};
     PSK_TRY(tmp.ensure((size_t)2 * n * sizeof(double)));
     double *r = tmp.as<double>(), *t = r + n;
     hipEvent_t e0, e1;
@@ -325,10 +322,7 @@ int psk_prec_create_chebyshev(const psk_csr *A, int32_t degree, double lmax, dou
     // apply), their maximum to scal[0], the bad-diagonal flag to the word behind it
     const int64_t nb = (n + kBlock - 1) / kBlock;
     DevBuf scal;
-    struct Release {
-        DevBuf &b;
-        ~Release() { b.release(); }
-    } rel{scal};
+    DevBufRelease rel{scal};
     PSK_TRY(scal.ensure(2 * sizeof(double)));
     double *gmax = scal.as<double>();
     int32_t *bad = reinterpret_cast<int32_t *>(gmax + 1);

@@ -21,6 +21,7 @@
 // Reference defects: self.precond never set (:71) -> we always form M;
 // NameError at maxiter (:180) -> we return the MAXITER status handleMaxiter would have built.
 #include "psk_internal.hpp"
+#include "dist.hpp"
 #include "solve_loop.hpp"
 
 #include <cmath>

@@ -4,11 +4,13 @@
 // enrolment count of the last sync-free triangular-solve launch. Declared in include/psk_lab.h; nothing in the
 // product path calls them.
 #include "amg.hpp"
+#include "dist.hpp"
 #include "trisolve.hpp"
 #include "pcg_state.hpp"
 #include "solve_loop.hpp"
 #include "../../include/psk_lab.h"
 
+#include <algorithm>
 #include <chrono>
 #include <string>
 
@@ -177,6 +179,35 @@ extern "C" int psk_lab_trisolve_plan(int64_t n, const int32_t *rowptr, const int
     const int64_t v[8] = {T.levels, T.band.K, T.band.nblocks, T.band.ring_words, T.band.narrow ? 1 : 0,
                           T.grid.K, T.grid.dict_n, T.lv.steps};
     for (int i = 0; i < 8; ++i) info[i] = v[i];
+    return PSK_OK;
+}
+
+// the host shard planner's view of one rank's block (no GPU, no Context): what psk_csr_create_dist plans and uploads
+extern "C" int psk_lab_dist_plan(int64_t n_global, const int64_t *row_starts, int32_t P, int32_t rank,
+                                 const int64_t *rowptr, const int32_t *colidx, int32_t *lcol, int64_t *halo,
+                                 int64_t *nhalo, int32_t *pack, int64_t *npack, int64_t *peers, int32_t *npeers) {
+    using namespace psk;
+    if (!row_starts || !rowptr || P < 1 || rank < 0 || rank >= P || !lcol || !halo || !nhalo || !pack || !npack || !peers ||
+        !npeers)
+        return fail(PSK_ERR_ARG, "psk_lab_dist_plan: bad arguments");
+    if (rowptr[row_starts[rank + 1] - row_starts[rank]] > rowptr[0] && !colidx)
+        return fail(PSK_ERR_ARG, "psk_lab_dist_plan: NULL entries");
+    DistPlan pl;
+    PSK_TRY(dist_plan(n_global, row_starts, P, rank, rowptr, colidx, pl));
+    std::vector<HaloPeer> hp;
+    std::vector<int32_t> pk;
+    dist_peers(pl, hp, pk);
+    std::copy(pl.lcol.begin(), pl.lcol.end(), lcol);
+    std::copy(pl.halo.begin(), pl.halo.end(), halo);
+    std::copy(pk.begin(), pk.end(), pack);
+    *nhalo = (int64_t)pl.halo.size();
+    *npack = (int64_t)pk.size();
+    *npeers = (int32_t)hp.size();
+    for (size_t k = 0; k < hp.size(); ++k) {
+        const HaloPeer &p = hp[k];
+        const int64_t v[7] = {p.rank, p.send_count, p.send_begin, p.packed ? 1 : 0, p.pack_off, p.recv_count, p.recv_offset};
+        std::copy(v, v + 7, peers + 7 * k);
+    }
     return PSK_OK;
 }
 

@@ -15,6 +15,7 @@
 // u is never stored: K2 and K3 both recompute u_i = DInv_i * r_i (one rounding, as np.multiply).
 // Elementwise updates use two roundings (-ffp-contract=off), exactly as numpy's x + alpha*p.
 #include "psk_internal.hpp"
+#include "dist.hpp"
 #include "pcg_state.hpp"
 
 #include <cstdlib>

@@ -132,10 +132,7 @@ int psk_prec_apply(const psk_prec *M, int64_t n, const double *v, double *outv, 
         return PSK_OK;
     }
     DevBuf tmp;
-    struct Release {   // (DevBuf has no destructor: the staging buffer was leaked before round 5)
-        DevBuf &b;
-        ~Release() { b.release(); }
-    } rel{tmp};
+    DevBufRelease rel{tmp};
     const double *dv = v;
     double *dout = outv;
     if (loc == PSK_HOST || v == outv) {

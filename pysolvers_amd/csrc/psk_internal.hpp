@@ -2,7 +2,6 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <cstdint>
 #include <cstring>
@@ -36,13 +35,6 @@ const char *hip_err_str(hipError_t e);
         hipError_t _e = (call);                                                               \
         if (_e != hipSuccess)                                                                 \
             return ::psk::fail(PSK_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-#define PSK_RCCL(call)                                                                           \
-    do {                                                                                         \
-        ncclResult_t _r = (call);                                                                \
-        if (_r != ncclSuccess)                                                                   \
-            return ::psk::fail(PSK_ERR_RCCL, std::string(#call) + ": " + ncclGetErrorString(_r)); \
     } while (0)
 
 #define PSK_TRY(call)              \
@@ -96,7 +88,6 @@ int comm_stream(Context *c, hipStream_t *out);
 int solve_kit(Context *c, bool timed, SolveKit **out);
 // true once psk_shutdown ran: destroy entry points become no-ops (the process is exiting)
 bool lib_shut_down();
-void rccl_comm_count(int delta);   // live RCCL communicators (psk_shutdown_ex resets the device only at 0)
 
 // ---------------------------------------------------------------------------------------------
 // grow-only device buffer
@@ -107,6 +98,12 @@ struct DevBuf {
     void release();
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
+// releases a function's temporary DevBuf on every return path (DevBuf has no destructor: the matrices'
+// grow-only buffers outlive the calls that fill them; prec.hip's staging buffer was leaked before round 5)
+struct DevBufRelease {
+    DevBuf &b;
+    ~DevBufRelease() { b.release(); }
+};
 
 // halo exchange plan of a row-block sharded matrix: local vector layout [owned | halo]
 struct HaloPeer {
@@ -114,57 +111,23 @@ struct HaloPeer {
     int64_t send_count;   // owned entries we send to this peer
     int64_t recv_count;   // halo entries we receive from it
     int64_t recv_offset;  // offset inside the halo region
-    int32_t *send_idx;    // device: owned local indices to pack (nullptr when contiguous); points
-                          // into psk_csr::pack_idx (not owned)
-    int64_t send_begin;   // contiguous owned range start when send_idx == nullptr
+    bool packed;          // the sent rows are not one contiguous run: gathered through psk_csr::pack_idx + pack_off
+    int64_t send_begin;   // contiguous owned range start when !packed
     int64_t pack_off;     // offset of this peer's packed segment in pack_idx / sendbuf
 };
 
-struct ShmComm;
 struct DenseInverse;
 struct Chebyshev;
 // largest dense coarse inverse (psk_prec_create_dense_inverse): 32768^2 doubles = 8.6 GB
 constexpr int64_t kDenseMaxN = 32768;
 
-// Device-side exchange of the solvers' per-rank scalars through a host-shared mailbox (dist.hip,
-// psk_comm_mailbox; round 5): the kernel that finishes a rank's grid sums stores them straight into
-// every rank's slot of the exchange (system-scope stores to pinned host memory mapped by all ranks of
-// the node), and a one-wave kernel on each rank waits for the P values of its own slot, copies them to
-// the gathered array the solver sums in rank order and re-arms the slot. Slot index (reader q, ring
-// position e mod kMbRing of exchange e, writer r, component c): ((q*kMbRing + e%kMbRing)*P + r)*kMbW + c.
-constexpr int kMbRing = 4;
-constexpr int kMbW = 2;
-struct Mailbox {
-    std::string name;
-    char *host = nullptr;     // the mapped segment (4 KiB header, then the slots)
-    size_t bytes = 0;
-    uint64_t *dev = nullptr;  // device address of the slots
-    int P = 1, rank = 0;
-    uint64_t seq = 0;         // exchanges issued on this communicator (identical on every rank)
-};
+// The distributed layer's types are defined in dist.hpp, which only the translation units that use a
+// communicator include; a matrix just points to its communicator.
+struct ShmComm;
+struct Mailbox;
 }  // namespace psk
 
-struct psk_comm {
-    int nranks = 1;
-    int rank = 0;
-    int device = 0;
-    ncclComm_t nccl = nullptr;
-    bool dry = false;     // psk_comm_init_dry: builds shards, no collectives (single-GPU validation)
-    psk::ShmComm *shm = nullptr;   // psk_comm_init_host: shared-memory transport (shmcomm.hip)
-    psk::Mailbox *mb = nullptr;    // psk_comm_mailbox: device-side scalar exchange (dist.hip)
-};
-
-namespace psk {
-// shared-memory transport (shmcomm.hip): stream-ordered like the RCCL calls they stand in for
-int shm_allgather(psk_comm *c, const double *send, double *recv, int64_t count, hipStream_t s);
-int shm_exchange(psk_comm *c, int npeers, const int *peers, const double *const *sends, const int64_t *send_counts,
-                 double *const *recvs, const int64_t *recv_counts, hipStream_t s);
-int shm_allgather_host(psk_comm *c, const void *mine, void *all, size_t bytes);
-int shm_exchange_host(psk_comm *c, int npeers, const int *peers, const void *const *sends, const size_t *send_bytes,
-                      void *const *recvs, const size_t *recv_bytes);
-int shm_error(const psk_comm *c);
-void shm_close(psk_comm *c);
-}  // namespace psk
+struct psk_comm;
 
 struct psk_csr {
     int64_t n = 0;        // local (owned) rows
@@ -933,21 +896,6 @@ inline int grid_for_rows(const Context *c, int64_t rows, int per_tile) {
 // host helpers shared by the solver TUs
 int to_device_vec(const double *src, int32_t loc, int64_t n, double *dst, hipStream_t s);
 int from_device_vec(const double *src, int32_t loc, int64_t n, double *dst, hipStream_t s);
-int halo_exchange(psk_csr *A, double *x_local, hipStream_t s);
-// the exchange on stream cs after the work enqueued on s (ev_a), completion recorded in ev_b
-int halo_exchange_async(psk_csr *A, double *x, hipStream_t s, hipStream_t cs, hipEvent_t ev_a, hipEvent_t ev_b,
-                        hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
-// rows sent to peers confined to the first lo / the tiles from hi on (of nv tiles of `tile` rows)
-bool halo_split(const psk_csr *A, int64_t tile, int64_t nv, int64_t &lo, int64_t &hi);
-// recv[q*count + i] = rank q's send[i]: no arithmetic, so every rank holds the same bits and
-// reduces them in rank order itself (RCCL's reduction order is algorithm- and rank-dependent)
-int allgather(psk_csr *A, const double *send, double *recv, int64_t count, hipStream_t s);
-// mailbox exchanges (psk_comm::mb): the next exchange's writer slots into gs (producer launch), and the
-// gather of that exchange into recv[q*W + c] on s (skipped on the device when *done is set: the producer
-// did not run either); returns the exchange number
-uint64_t mbox_next(psk_comm *c, GridSum *gs);
-int mbox_gather(psk_comm *c, uint64_t seq, int W, double *recv, const int32_t *done, hipStream_t s,
-                hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 
 // SpMV launch (defined in spmv.hip); modes below
 enum SpmvMode : int {

@@ -1,5 +1,6 @@
 // runtime.hip — error plumbing, per-device context, device-memory entry points.
 #include "psk_internal.hpp"
+#include "dist.hpp"
 
 #include <mutex>
 #include <atomic>

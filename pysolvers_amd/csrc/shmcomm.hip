@@ -13,9 +13,8 @@
 // collectives alternate, so a rank that runs ahead never overwrites data a slower rank has not
 // copied out yet: it cannot pass the next barrier before that rank's H2D, which precedes the
 // rank's next host function in stream order), each [P senders][P receivers][slot] bytes.
-#include "psk_internal.hpp"
+#include "dist.hpp"
 
-#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <fcntl.h>
@@ -36,18 +35,63 @@ struct ShmHeader {
 };
 
 struct ShmComm {
-    std::string name;
+    ShmSegment seg;
     int P = 1, r = 0;
-    size_t bytes = 0;
-    char *base = nullptr;
     int64_t barriers = 0;   // barriers this rank has entered (host-function order = stream order)
     int64_t gen = 0;        // collectives enqueued (parity buffer selection)
-    ShmHeader *hdr() const { return reinterpret_cast<ShmHeader *>(base); }
+    ShmHeader *hdr() const { return reinterpret_cast<ShmHeader *>(seg.base); }
     // slot of (sender, receiver) in parity buffer par
     char *slot(int64_t par, int snd, int rcv) const {
-        return base + kShmHeader + ((size_t)par * P * P + (size_t)snd * P + (size_t)rcv) * kShmSlot;
+        return seg.base + kShmHeader + ((size_t)par * P * P + (size_t)snd * P + (size_t)rcv) * kShmSlot;
     }
 };
+
+// ---- the named segment both this transport and the mailbox (dist_mailbox.hip) map: dist.hpp ShmSegment ----
+int shm_segment_open(ShmSegment &g, const char *who, const char *name, size_t bytes, unsigned register_flags,
+                     bool owner) {
+    const std::string w = std::string(who) + ": ";
+    const int fd = shm_open(name, O_CREAT | O_RDWR, 0600);
+    if (fd < 0) return fail(PSK_ERR_ARG, w + "shm_open " + name);
+    g.name = name;
+    g.bytes = bytes;
+    g.owner = owner;
+    struct stat st;
+    void *p = MAP_FAILED;
+    int rc = PSK_OK;
+    if (fstat(fd, &st) == 0 && (size_t)st.st_size < bytes && ftruncate(fd, (off_t)bytes) != 0)
+        rc = fail(PSK_ERR_ALLOC, w + "ftruncate");
+    else if ((p = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0)) == MAP_FAILED)
+        rc = fail(PSK_ERR_ALLOC, w + "mmap");
+    close(fd);
+    if (rc == PSK_OK) {
+        g.base = static_cast<char *>(p);
+        g.registered = hipHostRegister(g.base, bytes, register_flags) == hipSuccess;
+        if (!g.registered) {
+            (void)hipGetLastError();
+            rc = fail(PSK_ERR_HIP, w + "hipHostRegister of the shared segment");
+        }
+    }
+    if (rc != PSK_OK) shm_segment_close(g);
+    return rc;
+}
+
+int shm_segment_attach(const char *who, std::atomic<int32_t> *attached, int P) {
+    attached->fetch_add(1);
+    const auto t0 = std::chrono::steady_clock::now();
+    while (attached->load() < P) {
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60))
+            return fail(PSK_ERR_RCCL, std::string(who) + ": peers did not attach");
+        std::this_thread::yield();
+    }
+    return PSK_OK;
+}
+
+void shm_segment_close(ShmSegment &g) {
+    if (g.registered) (void)hipHostUnregister(g.base);
+    if (g.base) munmap(g.base, g.bytes);
+    if (g.owner && !g.name.empty()) shm_unlink(g.name.c_str());
+    g = ShmSegment();
+}
 
 static void shm_barrier(ShmComm *sc) {
     ShmHeader *h = sc->hdr();
@@ -139,14 +183,9 @@ int shm_exchange_host(psk_comm *c, int npeers, const int *peers, const void *con
 }
 
 void shm_close(psk_comm *c) {
-    ShmComm *sc = c->shm;
-    if (!sc) return;
-    if (sc->base) {
-        (void)hipHostUnregister(sc->base);
-        munmap(sc->base, sc->bytes);
-    }
-    if (sc->r == 0) shm_unlink(sc->name.c_str());
-    delete sc;
+    if (!c->shm) return;
+    shm_segment_close(c->shm->seg);
+    delete c->shm;
     c->shm = nullptr;
 }
 
@@ -157,49 +196,23 @@ using namespace psk;
 extern "C" int psk_comm_init_host(int32_t nranks, int32_t rank, const char *name, psk_comm **out) {
     if (!out || !name || nranks < 1 || rank < 0 || rank >= nranks || name[0] != '/' || std::strlen(name) > 200)
         return fail(PSK_ERR_ARG, "psk_comm_init_host: bad arguments (name must start with '/')");
+    const char *who = "psk_comm_init_host";
     ShmComm *sc = new ShmComm();
-    sc->name = name;
     sc->P = nranks;
     sc->r = rank;
-    sc->bytes = kShmHeader + 2 * (size_t)nranks * nranks * kShmSlot;
-    const int fd = shm_open(name, O_CREAT | O_RDWR, 0600);
-    if (fd < 0) {
-        delete sc;
-        return fail(PSK_ERR_ARG, std::string("psk_comm_init_host: shm_open ") + name);
-    }
-    struct stat st;
-    if (fstat(fd, &st) == 0 && (size_t)st.st_size < sc->bytes && ftruncate(fd, (off_t)sc->bytes) != 0) {
-        close(fd);
-        delete sc;
-        return fail(PSK_ERR_ALLOC, "psk_comm_init_host: ftruncate");
-    }
-    void *p = mmap(nullptr, sc->bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    close(fd);
-    if (p == MAP_FAILED) {
-        delete sc;
-        return fail(PSK_ERR_ALLOC, "psk_comm_init_host: mmap");
-    }
-    sc->base = static_cast<char *>(p);
-    if (hipHostRegister(sc->base, sc->bytes, hipHostRegisterDefault) != hipSuccess) {
-        munmap(sc->base, sc->bytes);
-        delete sc;
-        return fail(PSK_ERR_HIP, "psk_comm_init_host: hipHostRegister of the shared segment");
-    }
     psk_comm *c = new psk_comm();
     c->nranks = nranks;
     c->rank = rank;
     c->shm = sc;
     if (hipGetDevice(&c->device) != hipSuccess) c->device = 0;
+    int rc = shm_segment_open(sc->seg, who, name, kShmHeader + 2 * (size_t)nranks * nranks * kShmSlot,
+                              hipHostRegisterDefault, rank == 0);
     // every rank attached before anyone uses the segment (the creator's zero-filled header counts)
-    sc->hdr()->attached.fetch_add(1);
-    const auto t0 = std::chrono::steady_clock::now();
-    while (sc->hdr()->attached.load() < nranks) {
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(60)) {
-            shm_close(c);
-            delete c;
-            return fail(PSK_ERR_RCCL, "psk_comm_init_host: peers did not attach");
-        }
-        std::this_thread::yield();
+    if (rc == PSK_OK) rc = shm_segment_attach(who, &sc->hdr()->attached, nranks);
+    if (rc != PSK_OK) {
+        shm_close(c);
+        delete c;
+        return rc;
     }
     *out = c;
     return PSK_OK;

@@ -2,6 +2,7 @@
 // the empty shard's dot, then the layout's launcher), the layout chooser, and psk_spmv / psk_spmv_timed. The
 // kernels are in spmv_csr.hip, spmv_sliced.hip and spmv_diag.hip; what they share is in spmv.hpp.
 #include "spmv.hpp"
+#include "dist.hpp"
 #include "pcg_state.hpp"
 
 #include <cstdlib>

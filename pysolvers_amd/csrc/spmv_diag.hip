@@ -679,10 +679,7 @@ int diag_build(psk_csr *A, hipStream_t s, bool force) {
     if (n == 0 || A->nnz == 0) return no("empty matrix");
     if (nt > INT32_MAX) return no("too many slices");
     DevBuf tmp;
-    struct Release {
-        DevBuf &b;
-        ~Release() { b.release(); }
-    } rel{tmp};
+    DevBufRelease rel{tmp};
     PSK_TRY(tmp.ensure((size_t)nt * 2 * sizeof(int32_t) + 64));
     int32_t *dw = tmp.as<int32_t>(), *dspan = dw + nt;
     int32_t *dbad = dw + 2 * nt;

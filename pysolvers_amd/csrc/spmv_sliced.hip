@@ -559,10 +559,7 @@ static int find_value_dict(const psk_csr *A, hipStream_t s, std::vector<double> 
     dict.clear();
     if (A->nnz == 0) return PSK_OK;
     DevBuf tmp;
-    struct Release {
-        DevBuf &b;
-        ~Release() { b.release(); }
-    } rel{tmp};
+    DevBufRelease rel{tmp};
     PSK_TRY(tmp.ensure((size_t)(kDictMax + kDictCand + 1) * sizeof(double)));
     double *ddict = tmp.as<double>(), *dcand = ddict + kDictMax;
     int32_t *dn = reinterpret_cast<int32_t *>(dcand + kDictCand);
@@ -609,10 +606,7 @@ int sliced_build(psk_csr *A, hipStream_t s, bool force, bool pack, bool use_dict
     if (nt == 0) return PSK_OK;   // nothing to multiply (launch_spmv returns early)
     if (nt > INT32_MAX) return force ? fail(PSK_ERR_UNSUPPORTED, "sliced layout: too many slices") : PSK_OK;
     DevBuf tmp;
-    struct Release {
-        DevBuf &b;
-        ~Release() { b.release(); }
-    } rel{tmp};
+    DevBufRelease rel{tmp};
     PSK_TRY(tmp.ensure((size_t)nt * 2 * sizeof(int32_t)));
     int32_t *dw = tmp.as<int32_t>(), *dspan = dw + nt;
     PSK_TRY(sliced_shape(A, s, dw, dspan));

@@ -1,6 +1,6 @@
 // asan_host.cpp — AddressSanitizer / UBSan run of libpsk's host-only C++ (no GPU touched):
 // the MatrixMarket reader (psk_mm_info / psk_mm_read, mmio.hip), the smoothed-aggregation setup
-// (psk_sa_aggregate, amg_aggregate.hip) and the row-block sharding plan (psk_fd2d_dist_plan, dist.hip), on
+// (psk_sa_aggregate, amg_aggregate.hip) and the row-block sharding plan (psk_fd2d_dist_plan, dist_plan.hip), on
 // valid inputs and on malformed ones (every malformed file must be refused with an error code, never
 // read out of bounds). Built and run by scripts/asan_host.sh against a libpsk whose host code is
 // compiled with -fsanitize=address,undefined (device code unchanged); the log goes to profiles/.
