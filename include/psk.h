@@ -41,6 +41,7 @@
  *                    MLHierarchy.py:283-322) on the device, same bits in the same stored order.
  *   psk_csr_ilu0, psk_prec_create_ilu0: ILU(0) factored on the device; no reference counterpart (the
  *                    reference's incomplete factors are SuperLU's).
+ *   psk_prec_trisolve_sweeps: opt-in approximate triangular applies by Jacobi sweeps; no reference counterpart.
  */
 #ifndef PSK_H
 #define PSK_H
@@ -296,6 +297,31 @@ int psk_prec_trisolve_schedule(psk_prec *M, int32_t which, int32_t set, int32_t 
  * >> 1)), leading empty positions off, steps per 64-line band, dictionary records (0 = per-step
  * records). PSK_ERR_UNSUPPORTED when the factor is not a 2-D stencil. No compute (diagnostics, tests). */
 int psk_prec_trisolve_grid_info(const psk_prec *M, int32_t which, int64_t *out);
+/* Approximate solves of factor `which` (0 = L, 1 = U) of a triangular-solve chain by Jacobi sweeps.
+ * set >= 1: that many sweeps replace the factor's schedule in every later apply; set = 0: back to the exact
+ * schedule (psk_prec_trisolve_schedule's, untouched by this call); set = -1: query only. *sweeps (nullable)
+ * receives the value in force. Never chosen by the library itself.
+ *
+ * Arithmetic (all f64). The factor T is split into its off-diagonal entries N and its diagonal d; a unit factor
+ * has d = 1, its stored diagonal is ignored and nothing is divided. With b = rhs[rhs_idx] and s sweeps:
+ *     x(0)_i = b_i / d_i
+ *     x(j)_i = (b_i - sum_k N_ik x(j-1)_k) / d_i      j = 1..s        (IEEE division)
+ *     x      = x(s)
+ * A row's sum is formed by G = 1, 4, 16 or 64 lanes (chosen per factor from its mean off-diagonal row length:
+ * <= 2, <= 8, <= 32, more; PSK_TRISWEEP_WIDTH=1|4|16|64 in the environment when sweeps are set overrides it, for
+ * tests): lane t accumulates the row's entries t, t + G, ... in stored order with fma from 0.0, and the G lane
+ * sums are added in one fixed tree; b_i - sum and the division round separately. Every row of sweep j reads only
+ * x(j-1), never a value its own launch wrote (pure Jacobi on two alternating buffers), so the result is the same
+ * bits run after run. There is no dependency chain and no wait: one launch for x(0) and one per sweep on the apply's
+ * stream, nothing else synchronises. N is nilpotent: levels - 1 sweeps (psk_prec_info) give the exact solve up to
+ * the summation order. With a fixed s the apply is a fixed linear operator (GMRES, BiCGStab and PCG may use it;
+ * for a symmetric A the ILU(0) chain with equal counts stays symmetric).
+ *
+ * The first set >= 1 on a chain allocates two more n-vectors, freed by psk_prec_destroy. PSK_ERR_ARG when M is
+ * NULL or not a PSK_PREC_ILU, which is not 0 or 1, the factor is absent, set < -1 or set > 65536; PSK_ERR_ALLOC
+ * when the vectors cannot be allocated. On any error nothing changes. An AMG Gauss-Seidel smoother chain in
+ * sweep mode is honoured (the paired-sweep kernel steps aside). */
+int psk_prec_trisolve_sweeps(psk_prec *M, int32_t which, int32_t set, int32_t *sweeps);
 /* Host-only: the grid plan psk_prec_create_trisolve would make for one triangular factor (CSR with its
  * diagonal; upper = 1: solved from the last row up), without any device work — out[0..6] = w, H,
  * sigma2, phase, off, steps per band, record width K. PSK_ERR_UNSUPPORTED when it is not a 2-D stencil. */

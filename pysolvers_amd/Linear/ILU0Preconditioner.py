@@ -16,21 +16,32 @@ from .. import _native as N
 from .DeviceMatrix import as_device_matrix
 from .Preconditioner import DeviceOperator, LeftPreconditioner, Preconditioner, RightPreconditioner
 from .PreconditionerType import PreconditionerType
-from .TriangularSolve import TriangularSolveChain
+from .TriangularSolve import TriangularSolveChain, apply_sweeps
 
 
 class LeftILU0(PreconditionerType):
+    """sweeps: None (exact triangular solves), an int s or a pair (s_L, s_U): that many Jacobi sweeps replace the
+    solve of each factor (TriangularSolveChain.sweeps; 0 keeps a factor exact)."""
+
+    def __init__(self, sweeps=None):
+        self.sweeps = sweeps
+
     def form(self, A):
-        return LeftILU0Preconditioner(A)
+        return LeftILU0Preconditioner(A, sweeps=self.sweeps)
 
 
 class RightILU0(PreconditionerType):
+    """sweeps: as LeftILU0."""
+
+    def __init__(self, sweeps=None):
+        self.sweeps = sweeps
+
     def form(self, A):
-        return RightILU0Preconditioner(A)
+        return RightILU0Preconditioner(A, sweeps=self.sweeps)
 
 
 class ILU0Preconditioner(DeviceOperator, Preconditioner):
-    def __init__(self, A):
+    def __init__(self, A, sweeps=None):
         dA = as_device_matrix(A)
         if dA.comm is not None:
             raise ValueError("ILU(0) of a sharded matrix is not supported")
@@ -40,6 +51,7 @@ class ILU0Preconditioner(DeviceOperator, Preconditioner):
         self.n = dA.n
         self._A = dA        # for factors(); the handle itself borrows nothing
         self._F = None
+        apply_sweeps(self, sweeps)
 
     def factors(self):
         """F as a scipy CSR with sorted rows: L = strict-lower(F) with a unit diagonal, U = upper(F). The chain
@@ -51,9 +63,11 @@ class ILU0Preconditioner(DeviceOperator, Preconditioner):
             self._F = F
         return self._F
 
-    # schedule('L' | 'U', set=None) and grid_info: psk_prec_trisolve_schedule / _grid_info on the chain
+    # schedule('L' | 'U', set=None), grid_info and sweeps('L' | 'U', set=None): psk_prec_trisolve_schedule /
+    # _grid_info / _sweeps on the chain
     schedule = TriangularSolveChain.schedule
     grid_info = TriangularSolveChain.grid_info
+    sweeps = TriangularSolveChain.sweeps
 
 
 class LeftILU0Preconditioner(ILU0Preconditioner, LeftPreconditioner):

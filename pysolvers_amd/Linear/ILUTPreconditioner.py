@@ -17,6 +17,7 @@ from .. import _native as N
 from .DeviceMatrix import DeviceCSR
 from .Preconditioner import DeviceOperator, LeftPreconditioner, Preconditioner, RightPreconditioner
 from .PreconditionerType import PreconditionerType
+from .TriangularSolve import TriangularSolveChain, apply_sweeps
 
 
 def _host_matrix(A):
@@ -24,25 +25,27 @@ def _host_matrix(A):
 
 
 class LeftILUT(PreconditionerType):
-    def __init__(self, drop_tol=0.001, fill_factor=15):
+    def __init__(self, drop_tol=0.001, fill_factor=15, sweeps=None):
         self.drop_tol = drop_tol
         self.fill_factor = fill_factor
+        self.sweeps = sweeps   # None: exact solves; an int or (s_L, s_U): Jacobi sweeps (TriangularSolveChain.sweeps)
 
     def form(self, A):
-        return LeftILUTPreconditioner(A, drop_tol=self.drop_tol, fill_factor=self.fill_factor)
+        return LeftILUTPreconditioner(A, drop_tol=self.drop_tol, fill_factor=self.fill_factor, sweeps=self.sweeps)
 
 
 class RightILUT(PreconditionerType):
-    def __init__(self, drop_tol=0.001, fill_factor=15):
+    def __init__(self, drop_tol=0.001, fill_factor=15, sweeps=None):
         self.drop_tol = drop_tol
         self.fill_factor = fill_factor
+        self.sweeps = sweeps   # None: exact solves; an int or (s_L, s_U): Jacobi sweeps (TriangularSolveChain.sweeps)
 
     def form(self, A):
-        return RightILUTPreconditioner(A, drop_tol=self.drop_tol, fill_factor=self.fill_factor)
+        return RightILUTPreconditioner(A, drop_tol=self.drop_tol, fill_factor=self.fill_factor, sweeps=self.sweeps)
 
 
 class ILUTPreconditioner(DeviceOperator, Preconditioner):
-    def __init__(self, A, drop_tol=0.001, fill_factor=15):
+    def __init__(self, A, drop_tol=0.001, fill_factor=15, sweeps=None):
         Ah = _host_matrix(A)
         self._ILU = spla.spilu(Ah.tocsc(), drop_tol=drop_tol, fill_factor=fill_factor, diag_pivot_thresh=0.0)
         L = self._ILU.L.tocsr()
@@ -55,9 +58,14 @@ class ILUTPreconditioner(DeviceOperator, Preconditioner):
         h = ctypes.c_void_p()
         N.check(N.lib.psk_prec_create_ilu(self.n, *[N.ptr(a) for a in arr], ctypes.byref(h)), "psk_prec_create_ilu")
         self._h = h
+        apply_sweeps(self, sweeps)
 
     def ILU(self):
         return self._ILU
+
+    # schedule('L' | 'U', set=None) and sweeps('L' | 'U', set=None): psk_prec_trisolve_schedule / _sweeps on the chain
+    schedule = TriangularSolveChain.schedule
+    sweeps = TriangularSolveChain.sweeps
 
 
 class LeftILUTPreconditioner(ILUTPreconditioner, LeftPreconditioner):

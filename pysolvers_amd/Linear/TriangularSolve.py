@@ -31,6 +31,19 @@ def inverse_permutation(p):
     return inv
 
 
+def apply_sweeps(chain, sweeps):
+    """The ``sweeps=`` keyword of the ILU / IC preconditioner types, applied right after the chain is created:
+    None leaves the chain exact, an int s sets both factors, a pair (s_L, s_U) one each; 0 keeps a factor exact."""
+    if sweeps is None:
+        return
+    pair = (sweeps, sweeps) if isinstance(sweeps, (int, np.integer)) else tuple(sweeps)
+    if len(pair) != 2:
+        raise ValueError("sweeps must be None, an int or a pair (s_L, s_U)")
+    for which, s in zip(("L", "U"), pair):
+        if int(s) != 0:
+            chain.sweeps(which, int(s))
+
+
 class TriangularSolveChain(DeviceOperator, GenericPreconditioner):
     """out = (U^-1 L^-1 v[gather_in])[gather_out] on the device.
 
@@ -80,6 +93,16 @@ class TriangularSolveChain(DeviceOperator, GenericPreconditioner):
         return dict(schedule=("syncfree", "band", "lds", "grid", "part", "levels")[sc.value], blocks=bl.value,
                     ring_words=rw.value,
                     est_syncfree_us=e0.value, est_band_us=e1.value)
+
+    def sweeps(self, which, set=None):
+        """Jacobi sweeps in force for factor `which` ('L' or 'U'): 0 = the exact schedule. set=s >= 1 replaces the
+        factor's solve by s sweeps x <- D^-1 (b - N x) from x = D^-1 b in every later apply (an approximate solve:
+        streaming launches, no dependency waits); set=0 goes back to the exact schedule
+        (psk_prec_trisolve_sweeps)."""
+        out = N.I32()
+        N.check(N.lib.psk_prec_trisolve_sweeps(self._h, {"L": 0, "U": 1}[which], -1 if set is None else int(set),
+                                               ctypes.byref(out)), "psk_prec_trisolve_sweeps")
+        return out.value
 
     def grid_info(self, which):
         """Grid-schedule shape of factor `which` (psk_prec_trisolve_grid_info): dict(w, H, sigma2, phase, off,

@@ -94,7 +94,9 @@ static int amg_smooth(const AmgHierarchy *h, const Context *c, int lev, const do
     const int64_t n = A->n;
     double *r = h->r[lev].as<double>(), *t = h->t[lev].as<double>();
     int it = 0;
-    if ((size_t)lev < h->gp.size() && h->gp[lev].on)   // two sweeps per launch (gs_pair_kernel)
+    // two sweeps per launch (gs_pair_kernel), unless the smoother was switched to Jacobi sweeps since the hierarchy
+    // was built (psk_prec_trisolve_sweeps): the pair is an exact solve, so it steps aside for ilu_apply_add
+    if ((size_t)lev < h->gp.size() && h->gp[lev].on && h->S[lev]->up.sweeps == 0)
         for (; it + 2 <= nu; it += 2) {
             PSK_TRY(launch_spmv(A, kSpmvResid, x, r, nullptr, f, nullptr, nullptr, s));
             PSK_TRY(gs_pair_launch(c, h->gp[lev], h->S[lev], f, r, x, s));

@@ -504,6 +504,7 @@ int gs_pair_setup(psk_csr *A, psk_prec *S, GsPairLevel &g, hipStream_t s) {
     g = GsPairLevel();
     if (!A || !S || S->kind != PSK_PREC_ILU || S->lo.present || !S->up.present || S->up.fd5_m <= 0) return PSK_OK;
     if (S->gather_in || S->gather_out || !S->up.sched || !S->err || A->comm || !A->dg_mask || A->dg_K != 5) return PSK_OK;
+    if (S->up.sweeps != 0) return PSK_OK;   // a smoother in sweep mode (psk_prec_trisolve_sweeps) is not a Gauss-Seidel solve
 
     const TriFactor &U = S->up;
     const int64_t n = A->n, m = U.fd5_m;

@@ -151,7 +151,7 @@ int psk_prec_apply(const psk_prec *M, int64_t n, const double *v, double *outv, 
 
 int psk_prec_destroy(psk_prec *M) {
     if (!M || lib_shut_down()) return PSK_OK;   // after psk_shutdown: reclaimed with the process
-    void *ptrs[] = {M->dinv, M->gather_in, M->gather_out, M->work, M->err};
+    void *ptrs[] = {M->dinv, M->gather_in, M->gather_out, M->work, M->sweep_work, M->err};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     M->lo.release();

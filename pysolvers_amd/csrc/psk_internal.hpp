@@ -228,6 +228,12 @@ struct TriFactor {
     int schedule = kSchedSyncFree;
     uint32_t *sched = nullptr;      // block tickets / worker enrolment of the spin-waiting schedules (trisolve.hpp)
     double est_us[6] = {0.0, 0.0, -1.0, -1.0, -1.0, -1.0};   // the cost models' estimates by TriSchedule; -1: not eligible
+    // sweep mode (trisolve_sweep.hip; psk_prec_trisolve_sweeps): sweeps > 0 replaces `schedule` by that many Jacobi
+    // sweeps over the solve-order copy above with sweep_width lanes per row; sweep_buf = the chain's two iterate
+    // vectors (psk_prec::sweep_work, not owned). Never set by the library itself.
+    int32_t sweeps = 0;
+    int sweep_width = 0;
+    double *sweep_buf = nullptr;
     // band record stream (n records, block by block in local-level order; SoA, K entries each)
     struct Band {
         int32_t *rec_row = nullptr, *rec_end = nullptr, *rec_c = nullptr;
@@ -296,6 +302,7 @@ struct psk_prec {
     psk::TriFactor lo, up;
     int32_t *gather_in = nullptr, *gather_out = nullptr;
     double *work = nullptr;   // 2n: y, z
+    double *sweep_work = nullptr;   // 2n: the Jacobi-sweep iterates, allocated when sweep mode is first switched on
     int32_t *err = nullptr;
     psk::AmgHierarchy *amg = nullptr;   // PSK_PREC_AMG
     psk::DenseInverse *dense = nullptr; // PSK_PREC_DENSE (dense.hip)

@@ -12,8 +12,9 @@
 //
 // One file per schedule holds its kernel and launch (trisolve_syncfree.hip: sync-free and single-workgroup LDS;
 // trisolve_band.hip; trisolve_grid.hip; trisolve_levels.hip; trisolve_part.hip), trisolve_plan.hip the host
-// cost models that pick one and pack its layout, trisolve.hpp what they share. Here: the apply chain, the
-// upload of a plan and the C entry points.
+// cost models that pick one and pack its layout, trisolve.hpp what they share; trisolve_sweep.hip holds the opt-in
+// approximate apply by Jacobi sweeps (psk_prec_trisolve_sweeps). Here: the apply chain, the upload of a plan and
+// the C entry points.
 #include "trisolve.hpp"
 
 #include <string>
@@ -53,6 +54,7 @@ static int fill_factor_output(const TriFactor &T, int64_t n, double *x, hipStrea
 // x = T^-1 rhs[rhs_idx] for one factor, with the factor's schedule
 static int launch_factor(const Context *c, int64_t n, const TriFactor &T, const double *rhs, const int32_t *rhs_idx,
                          double *x, int32_t *err, hipStream_t s) {
+    if (T.sweeps > 0) return launch_sweeps(c, n, T, rhs, rhs_idx, x, err, s);   // opt-in (psk_prec_trisolve_sweeps)
     switch (T.schedule) {
     case kSchedLds: return launch_lds(c, n, T, rhs, rhs_idx, x, err, s);
     case kSchedLevel: return launch_levels(c, n, T, rhs, rhs_idx, x, err, s);
@@ -76,20 +78,24 @@ static int ilu_apply_impl(const psk_prec *M, const double *v, double *out, bool 
     const int nbuf = (M->lo.present ? 1 : 0) + (M->up.present ? 1 : 0);
     // factors whose schedule fills (or needs) no sentinel of its own: the grid schedule's published lines only,
     // none for the levels schedule
-    auto own_fill = [](const TriFactor &T) { return T.schedule == kSchedGrid || T.schedule == kSchedLevel; };
+    // none either for a factor in sweep mode (nothing waits): both swept, no fill at all
+    auto own_fill = [](const TriFactor &T) {
+        return T.sweeps > 0 || T.schedule == kSchedGrid || T.schedule == kSchedLevel;
+    };
     const bool grid_any = (M->lo.present && own_fill(M->lo)) || (M->up.present && own_fill(M->up));
     if (nbuf > 0 && !grid_any) {
         hipLaunchKernelGGL(fill_sentinel_kernel, dim3((unsigned)((nbuf * n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                            s, nbuf * n, y);   // y and z are contiguous
         PSK_HIP(hipGetLastError());
     } else if (nbuf > 0) {
-        if (M->lo.present) PSK_TRY(fill_factor_output(M->lo, n, y, s));
-        if (M->up.present) PSK_TRY(fill_factor_output(M->up, n, M->lo.present ? z : y, s));
+        if (M->lo.present && M->lo.sweeps == 0) PSK_TRY(fill_factor_output(M->lo, n, y, s));
+        if (M->up.present && M->up.sweeps == 0) PSK_TRY(fill_factor_output(M->up, n, M->lo.present ? z : y, s));
     }
     const double *cur = v;                // current right-hand side
     const int32_t *cur_idx = M->gather_in;
     const TriFactor &first = M->lo.present ? M->lo : M->up;
-    if (cur_idx && first.present && (first.schedule == kSchedGrid || first.schedule == kSchedPart)) {   // rhs[row]
+    if (cur_idx && first.present && first.sweeps == 0 &&
+        (first.schedule == kSchedGrid || first.schedule == kSchedPart)) {   // rhs[row]
         hipLaunchKernelGGL(gather_perm_kernel, dim3(fb), dim3(kBlock), 0, s, n, cur, cur_idx, M->work + 2 * n);
         PSK_HIP(hipGetLastError());
         cur = M->work + 2 * n;

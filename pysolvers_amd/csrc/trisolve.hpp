@@ -267,6 +267,10 @@ int plan_factor(int64_t n, const int32_t *rp, const int32_t *ci, const double *v
 using TriLaunch = int(const Context *c, int64_t n, const TriFactor &T, const double *rhs, const int32_t *rhs_idx,
                       double *x, int32_t *err, hipStream_t s);
 TriLaunch launch_syncfree, launch_lds, launch_part, launch_band, launch_grid, launch_levels;
+// T.sweeps Jacobi sweeps in place of the factor's schedule (trisolve_sweep.hip; psk_prec_trisolve_sweeps): plain
+// launches, no sentinel, no scheduling words, err never written
+TriLaunch launch_sweeps;
+constexpr int32_t kMaxSweeps = 65536;
 // the sentinel on the rows the grid schedule publishes (gate != nullptr: only when *gate is set)
 int launch_grid_fill(const TriFactor &T, int64_t n, double *x, const int32_t *gate, hipStream_t s);
 
