@@ -117,6 +117,26 @@ int psk_lab_solver_layout(int32_t solver, int64_t n, int64_t ncols, int64_t maxi
 int psk_lab_gmres_internals(const psk_csr *A, int64_t maxiter, int32_t restart, int32_t gen, int32_t cols, double *Q,
                             double *H, double *R, double *CS, double *g, double *y, double *state);
 int psk_lab_gmres_prefill(psk_csr *A, int64_t maxiter, int32_t restart, int32_t gen, int32_t byte);
+/* Tests of the PCG kernels (tests/test_gpu_pcg_kernels.py): what the last psk_pcg on the unsharded matrix A left in
+ * its workspace. psk_pcg carves A's two workspace buffers with one layout function and the buffers stay on the matrix
+ * after the solve; this carves them again for the same maxiter, gen (1: a general preconditioner, one that is
+ * neither none nor Jacobi) and own_x (1: the solve ran on host vectors, so x lives in the workspace; 0: x is the
+ * caller's device vector), waits for the library stream and copies to host arrays, any of which may be NULL.
+ * r[n], Ap[n]; ring[depth][ncols] with depth = psk_lab_pcg_stagger's *ring: row j = the buffer of p_i, i mod depth ==
+ * j (gen = 1 keeps one buffer, p in place: only row 0 is copied, the other rows are left as passed); u[n] is copied
+ * only with gen = 1 (the Jacobi / identity kernels never store u), x[n] only with own_x = 1; alphas, udr and hist have
+ * maxiter + 1 entries each (alphas[k] and udr[k + 1] are stored by K3 of an iteration k that did not end the solve;
+ * the general path stores no alphas); sums[3] = the last finished grid sums p.Ap, r.r and u.r (part1[0], part2[0] and
+ * part2[1]; with gen = 1 the third is pcg_dot_kernel's sum, part3[0]); state[8] = done, brk_kind, iters, resid, normB,
+ * tauNormB, live, x_written of the solve's device state. PSK_ERR_ARG when either buffer is smaller than that layout
+ * needs or the matrix is sharded. It reads only.
+ * psk_lab_pcg_prefill: psk_pcg clears none of these regions (each entry is written before it is read), so a test of
+ * what the kernels queued behind a stop leave untouched first grows A's two buffers to what that solve will ask for
+ * and sets every byte of both to `byte`; the solve then keeps the buffers. */
+int psk_lab_pcg_internals(const psk_csr *A, int64_t maxiter, int32_t gen, int32_t own_x, double *r, double *ring,
+                          double *Ap, double *u, double *x, double *alphas, double *udr, double *hist, double *sums,
+                          double *state);
+int psk_lab_pcg_prefill(psk_csr *A, int64_t maxiter, int32_t gen, int32_t own_x, int32_t byte);
 /* Measurement (tools/ilu0_ab.py): where the last psk_csr_ilu0 / psk_prec_create_ilu0 of this process spent its time.
  * out[0..6] = ms of the column sort and structure checks, of the pattern download and dependency levels, of the
  * numeric launches (HIP events around them), of the value download and L / U split, of psk_prec_create_trisolve

@@ -143,6 +143,8 @@ LAB_SIGNATURES = {
                                             ctypes.POINTER(I32), ctypes.POINTER(I64)]),
     "psk_lab_gmres_internals": (ctypes.c_int, [P, I64, I32, I32, I32, P, P, P, P, P, P, P]),
     "psk_lab_gmres_prefill": (ctypes.c_int, [P, I64, I32, I32, I32]),
+    "psk_lab_pcg_internals": (ctypes.c_int, [P, I64, I32, I32, P, P, P, P, P, P, P, P, P, P]),
+    "psk_lab_pcg_prefill": (ctypes.c_int, [P, I64, I32, I32, I32]),
     "psk_lab_ilu0_timing": (ctypes.c_int, [ctypes.POINTER(F64)]),
 }
 _lab = None

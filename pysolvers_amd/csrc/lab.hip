@@ -381,6 +381,66 @@ extern "C" int psk_lab_pcg_flush(int64_t n, int64_t k, int32_t stag, double *x, 
     return rc;
 }
 
+// ---- psk_pcg's workspace after a solve (pcg.hip pcg_work_view): what K0 .. K3 and the flush left in HBM ----
+extern "C" int psk_lab_pcg_internals(const psk_csr *A, int64_t maxiter, int32_t gen, int32_t own_x, double *r,
+                                     double *ring, double *Ap, double *u, double *x, double *alphas, double *udr,
+                                     double *hist, double *sums, double *state) {
+    using namespace psk;
+    if (!A) return fail(PSK_ERR_ARG, "psk_lab_pcg_internals: bad arguments");
+    PcgView v;
+    PSK_TRY(pcg_work_view(const_cast<psk_csr *>(A), maxiter, gen != 0, own_x != 0, false, &v));
+    Context *c;
+    PSK_TRY(ctx(&c));
+    PSK_HIP(hipStreamSynchronize(c->stream));
+    const size_t vec = (size_t)v.n * 8, vecc = (size_t)v.ncols * 8, it = (size_t)(maxiter + 1) * 8;
+    if (r && vec) PSK_HIP(hipMemcpy(r, v.r, vec, hipMemcpyDeviceToHost));
+    if (Ap && vec) PSK_HIP(hipMemcpy(Ap, v.Ap, vec, hipMemcpyDeviceToHost));
+    if (u && v.u && vec) PSK_HIP(hipMemcpy(u, v.u, vec, hipMemcpyDeviceToHost));
+    if (x && v.x && vec) PSK_HIP(hipMemcpy(x, v.x, vec, hipMemcpyDeviceToHost));
+    for (int t = 0; t < kPcgDefer; ++t)
+        if (ring && v.ring[t] && vecc)
+            PSK_HIP(hipMemcpy(ring + (size_t)t * (size_t)v.ncols, v.ring[t], vecc, hipMemcpyDeviceToHost));
+    if (alphas) PSK_HIP(hipMemcpy(alphas, v.alphas, it, hipMemcpyDeviceToHost));
+    if (udr) PSK_HIP(hipMemcpy(udr, v.udr, it, hipMemcpyDeviceToHost));
+    if (hist) PSK_HIP(hipMemcpy(hist, v.hist, it, hipMemcpyDeviceToHost));
+    if (sums) {
+        PSK_HIP(hipMemcpy(&sums[0], v.part1, 8, hipMemcpyDeviceToHost));
+        PSK_HIP(hipMemcpy(&sums[1], v.part2, 8, hipMemcpyDeviceToHost));
+        // u.r: K2 fuses it on the Jacobi / identity paths; the general path's is pcg_dot_kernel's (part3)
+        PSK_HIP(hipMemcpy(&sums[2], gen ? v.part3 : v.part2 + 1, 8, hipMemcpyDeviceToHost));
+    }
+    if (state) {
+        PcgState hs;
+        PSK_HIP(hipMemcpy(&hs, v.st, sizeof(hs), hipMemcpyDeviceToHost));
+        state[0] = (double)hs.done;
+        state[1] = (double)hs.brk_kind;
+        state[2] = (double)hs.iters;
+        state[3] = hs.resid;
+        state[4] = hs.normB;
+        state[5] = hs.tauNormB;
+        state[6] = (double)hs.live;
+        state[7] = (double)hs.x_written;
+    }
+    return PSK_OK;
+}
+
+// psk_pcg clears none of its vectors or scalar arrays (each entry is written before it is read): a test of what the
+// kernels leave untouched sets both buffers to a known byte first, sized as the solve will size them, so the solve
+// keeps them
+extern "C" int psk_lab_pcg_prefill(psk_csr *A, int64_t maxiter, int32_t gen, int32_t own_x, int32_t byte) {
+    using namespace psk;
+    if (!A || byte < 0 || byte > 255) return fail(PSK_ERR_ARG, "psk_lab_pcg_prefill: bad arguments");
+    Context *c;
+    PSK_TRY(ctx(&c));
+    PSK_HIP(hipStreamSynchronize(c->stream));   // a solve still queued on this matrix keeps its workspace
+    PcgView v;
+    PSK_TRY(pcg_work_view(A, maxiter, gen != 0, own_x != 0, true, &v));
+    PSK_HIP(hipMemsetAsync(v.big, byte, v.big_bytes, c->stream));
+    PSK_HIP(hipMemsetAsync(v.small, byte, v.small_bytes, c->stream));
+    PSK_HIP(hipStreamSynchronize(c->stream));
+    return PSK_OK;
+}
+
 // ---- the solvers' workspace layouts (solve_loop.hpp Carve) on null-based carvers: no GPU, no Context ----
 extern "C" int psk_lab_solver_layout(int32_t solver, int64_t n, int64_t ncols, int64_t maxiter, int64_t restart,
                                      int32_t flags, int32_t P, int64_t *offsets, int32_t *count, int64_t *bytes) {

@@ -445,6 +445,44 @@ static int pcg_workspace(psk_csr *A, int64_t maxiter, bool gen, bool own_x, int 
     return PSK_OK;
 }
 
+// the regions psk_pcg(maxiter, gen, own_x) carved on this unsharded matrix. grow: size the two buffers first (a
+// later solve then keeps them); otherwise PSK_ERR_ARG when either is smaller than the layout. Host code only
+// (psk_lab_pcg_internals, psk_lab_pcg_prefill).
+int pcg_work_view(psk_csr *A, int64_t maxiter, bool gen, bool own_x, bool grow, PcgView *v) {
+    if (!A || !v || maxiter < 0 || A->n < 0) return fail(PSK_ERR_ARG, "pcg_work_view: bad arguments");
+    if (A->comm) return fail(PSK_ERR_ARG, "pcg_work_view: sharded matrix");
+    int64_t need[2];
+    pcg_layout_probe(A->n, A->ncols, maxiter, gen, own_x, 1, nullptr, need);
+    if (grow) {
+        PSK_TRY(A->ws.ensure((size_t)need[0]));
+        PSK_TRY(A->ws_small.ensure((size_t)need[1]));
+    }
+    if (!A->ws.p || !A->ws_small.p || A->ws.bytes < (size_t)need[0] || A->ws_small.bytes < (size_t)need[1])
+        return fail(PSK_ERR_ARG, "pcg_work_view: the matrix's workspace is smaller than this layout");
+    Carve big{A->ws.as<char>()}, sm{A->ws_small.as<char>()};
+    PcgWork w;
+    pcg_layout(big, sm, A->n, A->ncols, maxiter, gen, own_x, 1, w);
+    v->n = A->n;
+    v->ncols = A->ncols;
+    v->r = w.r;
+    v->Ap = w.Ap;
+    v->x = w.x;
+    v->u = w.u;
+    for (int t = 0; t < kPcgDefer; ++t) v->ring[t] = w.pr.b[t];
+    v->part1 = w.part1;
+    v->part2 = w.part2;
+    v->part3 = w.part3;
+    v->udr = w.udr;
+    v->hist = w.hist;
+    v->alphas = w.alphas;
+    v->st = w.st;
+    v->big = A->ws.p;
+    v->big_bytes = (size_t)need[0];
+    v->small = A->ws_small.p;
+    v->small_bytes = (size_t)need[1];
+    return PSK_OK;
+}
+
 // psk_pcg's choice of the staggered x flush for a solve of A with preconditioner M (the lab library asks too)
 bool pcg_staggers(const psk_csr *A, const psk_prec *M) {
     return kPcgStagger > 0 && !prec_is_general(M) && !A->comm && A->n > 0 && spmv_flush_eligible(A);

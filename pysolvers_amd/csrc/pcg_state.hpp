@@ -201,4 +201,18 @@ int launch_pcg_flush(int64_t n, double *x, const PRing &pr, const double *alphas
 int launch_pcg_init_diag(const psk_csr *A, const double *b, double xs, double *p, double *Ap, double *out3,
                          const PcgInitFin &fin, hipStream_t s);
 
+// psk_pcg's workspace as the lab library reads it after a solve (pcg.hip pcg_work_view): device pointers into the
+// matrix's two buffers. x: null unless own_x; u and ring[1 ..]: null unless / when gen (the general path keeps one
+// p buffer); part1[0] = p.Ap, part2[0..1] = K2's (r.r, u.r) and, gen, part3[0] = pcg_dot_kernel's u.r: the last
+// finished grid sums.
+struct PcgView {
+    int64_t n, ncols;
+    double *r, *Ap, *x, *u, *ring[kPcgDefer];
+    double *part1, *part2, *part3, *udr, *hist, *alphas;
+    const PcgState *st;
+    void *big, *small;  // the two buffers and the bytes of each this layout covers
+    size_t big_bytes, small_bytes;
+};
+int pcg_work_view(psk_csr *A, int64_t maxiter, bool gen, bool own_x, bool grow, PcgView *v);
+
 }  // namespace psk
