@@ -433,6 +433,41 @@ int psk_gmres(const psk_csr *A, const psk_prec *M, const double *b, double *x, c
  * PSK_ERR_UNSUPPORTED. */
 int psk_bicgstab(const psk_csr *A, const psk_prec *M, const double *b, double *x, const psk_ctl *ctl,
                  psk_result *res, double *hist, int32_t loc);
+/* Preconditioned MINRES for SYMMETRIC INDEFINITE A (no reference counterpart): Paige-Saunders MINRES in the
+ * operation order of scipy.sparse.linalg.minres, with an SPD preconditioner M, x0 = 0, no shift; one SpMV, two dot
+ * products and a fixed footprint per iteration (ctl->restart is ignored). Every elementwise operation rounded once:
+ *   r1 = b; z = M^-1 r1; beta1^2 = r1.z        (< 0: preconditioner not positive definite; == 0: b = 0 exit)
+ *   normB = sqrt(b.b) (or ctl->norm_b); scale = normB / beta1 (exactly 1 for the identity)
+ *   oldb = 0; beta = beta1; dbar = epsln = 0; phibar = beta1; cs = -1; sn = 0; w = w2 = 0; r2 = r1
+ *   k = 0, 1, ...:
+ *     s = 1/beta; v = s z
+ *     y = A v;  k >= 1: y = y - (beta/oldb) r1
+ *     alfa = v.y                                  (AFTER the r1 term: the stable ordering, and scipy's)
+ *     y = y - (alfa/beta) r2;  r1 = r2;  r2 = y;  z = M^-1 r2
+ *     oldb = beta;  beta^2 = r2.z  (< 0: preconditioner not positive definite);  beta = sqrt(.)
+ *     oldeps = epsln; delta = cs dbar + sn alfa; gbar = sn dbar - cs alfa; epsln = sn beta; dbar = -cs beta
+ *     gamma = sqrt(gbar^2 + beta^2)               (== 0: breakdown, singular system)
+ *     cs = gbar/gamma; sn = beta/gamma; phi = cs phibar; phibar = sn phibar
+ *     w1 = w2; w2 = w; w = (v - oldeps w1 - delta w2) (1/gamma);  x = x + phi w
+ *     hist[k] = scale phibar
+ *     hist[k] <= tau normB, or k == maxiter-1 and !fail_on_maxiter: stop
+ * (v is stored and y = A v runs on it, so the iterates are scipy's to rounding. b.z == 0 with b != 0 is refused like
+ * b.z < 0.)
+ * THE NORM IN WHICH CONVERGENCE IS JUDGED: phibar is ||r_k|| in the M^-1 norm, sqrt(r.M^-1 r), the quantity MINRES
+ * minimises; hist[k] is scaled so that hist[k] / norm_b is the relative reduction in that norm. With the identity it
+ * is ||b - A x_k||_2. Under a preconditioner the 2-norm residual is bounded by ||r||_2/||b||_2 <= sqrt(cond(M)) tau,
+ * not by tau. A Krylov space that is exhausted gives beta = 0, hence phibar = 0, and leaves by the ordinary test.
+ * Stopping at iteration k: PSK_CONVERGED, iters = k+1, hist_len = k+1; on a tolerance exit (PSK_EXIT_TOLERANCE)
+ * resid = the true ||b - A x||_2, measured by one more SpMV, and resid_recursive = hist[k]. With the identity a true
+ * residual above tau*normB is PSK_TRUE_RESID_FAIL (as psk_gmres); under a preconditioner the solve's contract is
+ * the preconditioned norm and the status stays converged. r.z < 0 (at the init: iters = 0; at iteration k:
+ * iters = k): PSK_BREAKDOWN, PSK_EXIT_DOT_BREAKDOWN, resid = NaN, "preconditioner not positive definite";
+ * gamma == 0: the same codes, "breakdown gamma==0". maxiter reached: PSK_MAXITER, iters = maxiter-1. b = 0: as
+ * psk_pcg. ctl->norm_b as for psk_gmres. spmv_launches counts the SpMV launches that did their work: one per
+ * iteration, plus the true residual's. A must be symmetric (not checked). A sharded A with more than one rank:
+ * PSK_ERR_UNSUPPORTED. */
+int psk_minres(const psk_csr *A, const psk_prec *M, const double *b, double *x, const psk_ctl *ctl,
+               psk_result *res, double *hist, int32_t loc);
 /* The standalone AMG V-cycle solver, AMGVCycleSolver.solve (VCycleSolver.py:52-95), on the device: M is a
  * PSK_PREC_AMG whose finest level matrix is the system matrix (PSK_ERR_ARG otherwise); its own num_iters and
  * tau are ignored, ctl->maxiter (> 0) and ctl->tau rule. x0 = copy(b) (:69), or the caller's x with

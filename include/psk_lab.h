@@ -87,15 +87,18 @@ int psk_lab_pcg_flush_schedule(int32_t S, int64_t nv, int64_t tile, int64_t k, i
 int psk_lab_pcg_flush(int64_t n, int64_t k, int32_t stag, double *x, const double *ring, const double *alphas);
 /* Tests of the solvers' workspace layouts (solve_loop.hpp Carve); touches no GPU. Runs the layout function of
  * `solver` on null-based carvers, the one its solve sizes and carves its buffers with: offsets[*count] = the byte
- * offset of every region in the order the layout takes them (PCG, GMRES, BiCGStab: the regions of the matrix's
+ * offset of every region in the order the layout takes them (PCG, GMRES, BiCGStab, MINRES: the regions of the matrix's
  * large workspace, then those of its small one, each counted from its own buffer's start), bytes[2] = the sizes the two
  * buffers are grown to (the V-cycle has one: bytes[1] = 0). On entry *count = the capacity of offsets.
  * PCG reads n, ncols, maxiter, flags (GEN, OWN_X) and P ranks; GMRES n, maxiter, restart, flags (GEN); the V-cycle
- * n, maxiter, flags (DEV_IO); BiCGStab n, maxiter, flags (GEN). */
+ * n, maxiter, flags (DEV_IO); BiCGStab n, maxiter, flags (GEN); MINRES n, maxiter, flags (GEN).
+ * Solver id 4 is not taken:
+ * tests/test_solver_layout.py keeps it as its example of an unknown solver. */
 #define PSK_LAB_SOLVER_PCG 0
 #define PSK_LAB_SOLVER_GMRES 1
 #define PSK_LAB_SOLVER_VCYCLE 2
 #define PSK_LAB_SOLVER_BICGSTAB 3
+#define PSK_LAB_SOLVER_MINRES 5
 #define PSK_LAB_LAYOUT_GEN 1    /* general preconditioner (u, GMRES's w and t, or BiCGStab's ph and sh, materialised) */
 #define PSK_LAB_LAYOUT_OWN_X 2  /* PCG: x in the workspace (host vectors), not the caller's device vector */
 #define PSK_LAB_LAYOUT_DEV_IO 4 /* V-cycle: b and x are the caller's device vectors (not staged) */

@@ -36,7 +36,7 @@ class IterativeLinearSolverType(LinearSolverType):
 class IterativeLinearSolver(LinearSolver, IterativeSolver):
     """Solver base (IterativeLinearSolver.py:60-86) + the device driver."""
 
-    _entry = None          # "psk_pcg" / "psk_gmres" / "psk_bicgstab"
+    _entry = None          # "psk_pcg" / "psk_gmres" / "psk_bicgstab" / "psk_minres"
     _method = "GMRES"      # the method's name in the true-residual failure text (GMRESSolver.py:167-174)
     # PCGSolver.solve prints 'prec frozen = ...' and 'building prec' on every solve with b != 0
     # (PCGSolver.py:91,93); PCGSolver sets this (class attribute: a driver may switch it off)
@@ -69,6 +69,11 @@ class IterativeLinearSolver(LinearSolver, IterativeSolver):
 
     def _restart(self):
         return 0
+
+    def _retests_true_residual(self, kind):
+        """With a caller's norm: is a tolerance exit under a preconditioner of device kind `kind` re-tested
+        against the true residual in that norm? GMRES and BiCGStab: always. MINRES: under the identity only."""
+        return True
 
     # -----------------------------------------------------------------------------------------
     def _device_matrix(self, A):
@@ -140,8 +145,9 @@ class IterativeLinearSolver(LinearSolver, IterativeSolver):
         fn = getattr(N.lib, self._entry)
         N.check(fn(dA.handle, ph, N.ptr(bp), N.ptr(x), ctypes.byref(ctl), ctypes.byref(res), N.ptr(hist), loc),
                 self._entry)
-        if custom and res.exit in (N.PSK_EXIT_TOLERANCE, N.PSK_EXIT_ARNOLDI_BREAKDOWN):
-            # GMRES / BiCGStab stopped on the recursive residual: the true-residual test in the caller's norm
+        if custom and res.exit in (N.PSK_EXIT_TOLERANCE, N.PSK_EXIT_ARNOLDI_BREAKDOWN) and \
+                self._retests_true_residual(kind):
+            # GMRES / BiCGStab / MINRES stopped on the recursive residual: the true-residual test in the caller's norm
             # (GMRESSolver.py:163-174): resid = b - A x on the device, its norm by the caller's code
             rt = _host_copy(b) - _host_copy(spmv(dA, x))
             nrt = float(self.norm(rt))

@@ -13,6 +13,7 @@ from .ILU0Preconditioner import (ILU0Preconditioner, LeftILU0, LeftILU0Precondit
 from .ICPreconditioner import ICRightPreconditioner, RightIC
 from .IterativeLinearSolver import IterativeLinearSolver, IterativeLinearSolverType, mvmult
 from .LinearSolver import LinearSolver, LinearSolverType
+from .MINRESSolver import MINRES, MINRESSolver
 from .PCGSolver import PCG, PCGSolver
 from .MLHierarchy import MLHierarchy, makeRestrictionOp
 from .Preconditioner import (ChebyshevPreconditioner, DeviceOperator, GenericPreconditioner, IdentityPreconditioner,

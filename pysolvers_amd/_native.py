@@ -101,6 +101,7 @@ SIGNATURES = {
     "psk_pcg": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_gmres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_bicgstab": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
+    "psk_minres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_vcycle": (ctypes.c_int, [P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32, I32]),
     "psk_comm_unique_id": (ctypes.c_int, [P]),
     "psk_comm_init": (ctypes.c_int, [I32, I32, P, PP]),

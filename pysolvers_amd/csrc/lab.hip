@@ -452,6 +452,7 @@ extern "C" int psk_lab_solver_layout(int32_t solver, int64_t n, int64_t ncols, i
     if (solver == PSK_LAB_SOLVER_PCG) pcg_layout_probe(n, ncols, maxiter, gen, (flags & PSK_LAB_LAYOUT_OWN_X) != 0, P, &log, bytes);
     else if (solver == PSK_LAB_SOLVER_GMRES) gmres_layout_probe(n, maxiter, restart, gen, &log, bytes);
     else if (solver == PSK_LAB_SOLVER_BICGSTAB) bicgstab_layout_probe(n, maxiter, gen, &log, bytes);
+    else if (solver == PSK_LAB_SOLVER_MINRES) minres_layout_probe(n, maxiter, gen, &log, bytes);
     else if (solver == PSK_LAB_SOLVER_VCYCLE) vcycle_layout_probe(n, maxiter, (flags & PSK_LAB_LAYOUT_DEV_IO) != 0, &log, bytes);
     else return fail(PSK_ERR_ARG, "psk_lab_solver_layout: unknown solver");
     if ((size_t)*count < log.size()) return fail(PSK_ERR_ARG, "psk_lab_solver_layout: offsets too short");

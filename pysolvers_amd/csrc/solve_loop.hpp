@@ -1,5 +1,5 @@
-// solve_loop.hpp — host-side helpers of the device-loop solvers (psk_pcg, psk_bicgstab, psk_gmres, psk_vcycle): the
-// workspace carver, the done-stamp poll and the psk_result lines all four write alike. Host code only: no kernel
+// solve_loop.hpp — host-side helpers of the device-loop solvers (psk_pcg, psk_bicgstab, psk_minres, psk_gmres, psk_vcycle): the
+// workspace carver, the done-stamp poll and the psk_result lines they all write alike. Host code only: no kernel
 // lives here (the kernels' side of the stamp is done_stamp_store, psk_internal.hpp).
 #pragma once
 #include "psk_internal.hpp"
@@ -28,6 +28,7 @@ void pcg_layout_probe(int64_t n, int64_t ncols, int64_t maxiter, bool gen, bool 
                       std::vector<int64_t> *log, int64_t *bytes);
 void gmres_layout_probe(int64_t n, int64_t maxiter, int64_t restart, bool gen, std::vector<int64_t> *log, int64_t *bytes);
 void bicgstab_layout_probe(int64_t n, int64_t maxiter, bool gen, std::vector<int64_t> *log, int64_t *bytes);
+void minres_layout_probe(int64_t n, int64_t maxiter, bool gen, std::vector<int64_t> *log, int64_t *bytes);
 void vcycle_layout_probe(int64_t n, int64_t maxiter, bool dev_io, std::vector<int64_t> *log, int64_t *bytes);
 
 // ---- what every solver writes into its psk_result the same way (res was zeroed by the entry point) ----
