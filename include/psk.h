@@ -42,6 +42,8 @@
  *   psk_csr_ilu0, psk_prec_create_ilu0: ILU(0) factored on the device; no reference counterpart (the
  *                    reference's incomplete factors are SuperLU's).
  *   psk_prec_trisolve_sweeps: opt-in approximate triangular applies by Jacobi sweeps; no reference counterpart.
+ *   psk_csr_fsai, psk_prec_create_fsai: factorized sparse approximate inverse G ~ L^-1 formed on the device and
+ *                    applied as two SpMVs; no reference counterpart.
  */
 #ifndef PSK_H
 #define PSK_H
@@ -406,6 +408,50 @@ int psk_csr_ilu0(const psk_csr *A, psk_csr **F);
  * psk_prec_apply, psk_prec_info, psk_prec_trisolve_schedule and the solvers take it like any other. Errors as
  * psk_csr_ilu0; A is not borrowed. Replaces nothing in the reference. */
 int psk_prec_create_ilu0(const psk_csr *A, psk_prec **out);
+
+/* ---- factorized sparse approximate inverse on the device (fsai.hip) ---------------------------- */
+/* G = the FSAI factor of a square, symmetric, definite A on a prescribed pattern: a sparse lower-triangular
+ * G ~ L^-1, where s A = L L^T and s = +-1 is A's sign, formed from n independent small dense problems. pattern == NULL
+ * means A's own pattern; otherwise pattern is a square device CSR of A's size of which only the structure is read,
+ * and its entries with column > row are ignored.
+ * Row i's index set: J = the pattern row's columns <= i in ascending order, m = |J|. J must contain i
+ * (PSK_ERR_ARG). A duplicate column within a row of A or of the pattern is PSK_ERR_UNSUPPORTED, and so is
+ * m > PSK_FSAI_ROW_CAP (psk_last_error names the smallest such row). Rows of A and of the pattern may be stored in
+ * any order (they are sorted into working copies first).
+ * Sign: s = +1 when row 0's stored diagonal entry of A is > 0, -1 when it is < 0 (zero, missing or not finite:
+ * PSK_ERR_ARG); *sign = s. The factorisation runs on s A, an exact sign flip, so a negative definite A (such as
+ * FDLaplacian2D(-1, 1, m)) is taken as Jacobi takes it.
+ * Arithmetic: all f64, every operation rounded once, a product rounded before its add or subtract (no FMA).
+ *   Submatrix, for 0 <= b <= a < m: B[a][b] = s * (the entry of row J[a] of A with column J[b], or 0.0 when it is not
+ *   stored). Only A's lower triangle is read; symmetry is not checked.
+ *   Cholesky, for b = 0..m-1 and a = b..m-1: t = B[a][b], then t = t - C[a][k] * C[b][k] for k = 0..b-1 in ascending
+ *   k. If a == b, t must be > 0 and finite (else PSK_ERR_ARG "not positive definite", psk_last_error naming the
+ *   smallest such row i) and C[b][b] = sqrt(t); otherwise C[a][b] = t / C[b][b] (IEEE division).
+ *   Back substitution for g = C^-T e_m: g[m-1] = 1.0 / C[m-1][m-1]; for a = m-2 down to 0: u = 0.0, then
+ *   u = u + C[b][a] * g[b] for b = a+1..m-1 ascending, and g[a] = (-u) / C[a][a].
+ *   Row i of G stores the columns J in ascending order with the values g.
+ * Every value's update sequence is fixed above, so the result does not depend on the launch geometry or on which of
+ * the two numeric kernels handled the row: one lane per row when every m <= 4 (stencils on their own pattern), one
+ * wave per row otherwise or when flags holds PSK_FSAI_WAVE_ONLY. No kernel waits for another wave.
+ * The result ends like psk_csr_create(..., PSK_DEVICE) (the SpMV layout choice applies) and psk_csr_download reads
+ * it back. *G and *sign are written only on success. A and the pattern are only read; nothing is borrowed.
+ * PSK_ERR_UNSUPPORTED also: a sharded A or pattern. PSK_ERR_ARG also: A not square or empty, a pattern of another
+ * size, a column outside [0, n), an unknown flag. Replaces nothing in the reference. */
+#define PSK_PREC_FSAI      6       /* preconditioner kind: M^-1 v = G^T (G v) (psk_prec_create_fsai) */
+#define PSK_FSAI_ROW_CAP   64      /* longest pattern row (lower part, diagonal included) */
+#define PSK_FSAI_WAVE_ONLY 1       /* flags: every row through the general (wave-per-row) kernel */
+int psk_csr_fsai(const psk_csr *A, const psk_csr *pattern, int32_t flags, psk_csr **G, int32_t *sign);
+/* The FSAI preconditioner of A: psk_csr_fsai, then Gt = s G^T by psk_csr_transpose (the values flipped exactly when
+ * s = -1). M^-1 v = Gt (G v) ~ A^-1 v: t = G v, out = Gt t, two launches of the library's SpMV on the apply's stream
+ * with the bits of two psk_spmv calls. s M^-1 is symmetric positive definite by construction (G has a positive
+ * diagonal), so PCG and MINRES may use it on a definite A; GMRES, BiCGStab and the AMG smoother slot take it like
+ * any other. The preconditioner owns G, Gt and one n-vector; psk_prec_info reports kind PSK_PREC_FSAI,
+ * nnz_l = nnz_u = nnz(G) and 0 levels. Errors as psk_csr_fsai; A and the pattern are not borrowed. Replaces nothing
+ * in the reference. */
+int psk_prec_create_fsai(const psk_csr *A, const psk_csr *pattern, int32_t flags, psk_prec **out);
+/* The formed factor: A's sign, the entries of G and its longest row. Any out pointer may be NULL. PSK_ERR_ARG when M
+ * is not a PSK_PREC_FSAI. */
+int psk_prec_fsai_info(const psk_prec *M, int32_t *sign, int64_t *nnz_g, int32_t *max_row);
 
 /* ---- solvers ------------------------------------------------------------------------------ */
 /* M == NULL means identity. b, x: length n (local length for a distributed A); with loc ==

@@ -185,6 +185,20 @@ class DeviceCSR:
         N.check(N.lib.psk_csr_ilu0(self._h, ctypes.byref(h)), "psk_csr_ilu0")
         return DeviceCSR._adopt(h, self.ncols)
 
+    def fsai(self, pattern=None, flags=0):
+        """``(G, sign)``: the factorized sparse approximate inverse of this symmetric definite matrix as a lower
+        triangular DeviceCSR G ~ L^-1 (sign A = L L^T) on tril(pattern), formed on the device (psk_csr_fsai; the
+        arithmetic is defined to the bit in include/psk.h). ``pattern=None``: this matrix's own pattern; otherwise a
+        DeviceCSR (or scipy matrix) of this size whose structure alone is read. ``flags``: 0 or
+        ``PSK_FSAI_WAVE_ONLY``. Raises PskError with PSK_ERR_ARG for a pattern row without its diagonal or a matrix
+        that is not definite, PSK_ERR_UNSUPPORTED for a duplicate column or a pattern row longer than
+        PSK_FSAI_ROW_CAP."""
+        dP = None if pattern is None else as_device_matrix(pattern)
+        h, sign = ctypes.c_void_p(), N.I32()
+        N.check(N.lib.psk_csr_fsai(self._h, None if dP is None else dP.handle, int(flags), ctypes.byref(h),
+                                   ctypes.byref(sign)), "psk_csr_fsai")
+        return DeviceCSR._adopt(h, self.ncols), sign.value
+
     def to_scipy(self):
         indptr = np.empty(self.n + 1, dtype=np.int32)
         indices = np.empty(self.nnz, dtype=np.int32)

@@ -10,7 +10,7 @@ from abc import ABC, abstractmethod
 import numpy as np
 
 from .. import _native as N
-from .DeviceMatrix import DeviceVector, as_device_matrix, is_device_vector, torch_stream_ready
+from .DeviceMatrix import DeviceVector, as_device_matrix, is_device_vector, matmat, torch_stream_ready
 
 
 class Preconditioner(ABC):
@@ -181,6 +181,56 @@ class ChebyshevPreconditioner(DeviceOperator, GenericPreconditioner):
         c = np.empty(2 * self.degree - 1, dtype=np.float64)
         N.check(N.lib.psk_prec_chebyshev_info(self._h, None, None, None, N.ptr(c)), "psk_prec_chebyshev_info")
         return c
+
+    def apply(self, vec):
+        return self._device_apply(vec)
+
+
+class FSAIPreconditioner(DeviceOperator, GenericPreconditioner):
+    """M^-1 v = G^T (G v) with the factorized sparse approximate inverse G ~ L^-1 of a symmetric definite A
+    (sign A = L L^T) on the pattern of tril(A^power) (psk_prec_create_fsai, pysolvers_amd/csrc/fsai.hip).
+
+    No reference counterpart: the preconditioner that is formed by n independent small Cholesky factorisations on
+    the device and applied as two SpMVs, with no triangular solve, no level schedule and no eigenvalue bound. sign
+    M^-1 is symmetric positive definite by construction, so PCG and MINRES may use it. ``power=1`` takes A's own
+    pattern, ``power=2`` the pattern of A A (the device SpGEMM); a pattern row may hold at most PSK_FSAI_ROW_CAP
+    lower entries. A negative definite A (``sign`` = -1) is taken as Jacobi takes it.
+    """
+
+    device_kind = N.PSK_PREC_FSAI
+
+    def __init__(self, A, power=1):
+        if power not in (1, 2):
+            raise ValueError("FSAIPreconditioner: power must be 1 or 2")
+        dA = as_device_matrix(A)
+        pattern = matmat(dA, dA) if power == 2 else None     # read during the setup only
+        h = ctypes.c_void_p()
+        N.check(N.lib.psk_prec_create_fsai(dA.handle, None if pattern is None else pattern.handle, 0,
+                                           ctypes.byref(h)), "psk_prec_create_fsai")
+        self._h = h
+        self.n = dA.n
+        self.power = int(power)
+
+    def _info(self):
+        s, nnz, mr = N.I32(), N.I64(), N.I32()
+        N.check(N.lib.psk_prec_fsai_info(self._h, ctypes.byref(s), ctypes.byref(nnz), ctypes.byref(mr)),
+                "psk_prec_fsai_info")
+        return s.value, nnz.value, mr.value
+
+    @property
+    def sign(self):
+        """+1 / -1: the sign of A (of row 0's diagonal entry)."""
+        return self._info()[0]
+
+    @property
+    def nnz(self):
+        """Stored entries of G."""
+        return self._info()[1]
+
+    @property
+    def max_row(self):
+        """Longest row of G: the size of the largest dense problem of the setup."""
+        return self._info()[2]
 
     def apply(self, vec):
         return self._device_apply(vec)

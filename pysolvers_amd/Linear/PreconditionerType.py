@@ -1,7 +1,8 @@
 """Preconditioner factories (PreconditionerType.py:4-19): ``form(A)`` builds the operator."""
 from abc import ABC, abstractmethod
 
-from .Preconditioner import ChebyshevPreconditioner, IdentityPreconditioner, JacobiPreconditioner
+from .Preconditioner import (ChebyshevPreconditioner, FSAIPreconditioner, IdentityPreconditioner,
+                             JacobiPreconditioner)
 
 
 class PreconditionerType(ABC):
@@ -42,3 +43,16 @@ class ChebyshevPreconditionerType(PreconditionerType):
 
 
 Chebyshev = ChebyshevPreconditionerType
+
+
+class FSAIPreconditionerType(PreconditionerType):
+    """Factorized sparse approximate inverse on the pattern of tril(A^power) (FSAIPreconditioner), power 1 or 2."""
+
+    def __init__(self, power=1):
+        self.power = power
+
+    def form(self, A):
+        return FSAIPreconditioner(A, power=self.power)
+
+
+FSAI = FSAIPreconditionerType

@@ -16,9 +16,10 @@ from .LinearSolver import LinearSolver, LinearSolverType
 from .MINRESSolver import MINRES, MINRESSolver
 from .PCGSolver import PCG, PCGSolver
 from .MLHierarchy import MLHierarchy, makeRestrictionOp
-from .Preconditioner import (ChebyshevPreconditioner, DeviceOperator, GenericPreconditioner, IdentityPreconditioner,
-                             JacobiPreconditioner, LeftPreconditioner, Preconditioner, RightPreconditioner)
-from .PreconditionerType import (Chebyshev, ChebyshevPreconditionerType, IdentityPreconditionerType, Jacobi,
+from .Preconditioner import (ChebyshevPreconditioner, DeviceOperator, FSAIPreconditioner, GenericPreconditioner,
+                             IdentityPreconditioner, JacobiPreconditioner, LeftPreconditioner, Preconditioner, RightPreconditioner)
+from .PreconditionerType import (Chebyshev, ChebyshevPreconditionerType, FSAI, FSAIPreconditionerType,
+                                 IdentityPreconditionerType, Jacobi,
                                  JacobiPreconditionerType, PreconditionerType)
 from .SmoothedAggregation import SA_coarsen, SmoothedAggregationMLHierarchy
 from .TriangularSolve import TriangularSolveChain

@@ -8,10 +8,12 @@ from .IterativeSolver import CommonSolverArgs, IterativeSolver, NamedObject, Sol
 from .Linear import (AMG, AMGVCycle, AMGVCycleSolver, BiCGStab, BiCGStabSolver, DefaultDirect, GMRES, MINRES, MINRESSolver, PCG, RightIC, GaussSeidelSmoother, JacobiSmoother, DeviceCSR, DeviceVector, GMRESSolver, IdentityPreconditioner,
                      IdentityPreconditionerType, IterativeLinearSolver, Jacobi, JacobiPreconditioner,
                      JacobiPreconditionerType, LeftILUT, PCGSolver, RightILUT, mvmult,
-                     Chebyshev, ChebyshevPreconditioner, ChebyshevSmoother, LeftILU0, RightILU0)
+                     Chebyshev, ChebyshevPreconditioner, ChebyshevSmoother, LeftILU0, RightILU0,
+                     FSAI, FSAIPreconditioner, FSAIPreconditionerType)
 
 __all__ = ["Nonlinear", "AMG", "AMGVCycle", "AMGVCycleSolver", "BiCGStab", "BiCGStabSolver", "MINRES", "MINRESSolver", "DefaultDirect", "RightIC", "GaussSeidelSmoother", "JacobiSmoother", "Linear", "CommonSolverArgs", "IterativeSolver", "NamedObject", "SolveStatus", "GMRES", "PCG",
            "GMRESSolver", "PCGSolver", "DeviceCSR", "DeviceVector", "IdentityPreconditioner",
            "IdentityPreconditionerType", "IterativeLinearSolver", "Jacobi", "JacobiPreconditioner",
            "JacobiPreconditionerType", "LeftILUT", "RightILUT", "mvmult",
-           "Chebyshev", "ChebyshevPreconditioner", "ChebyshevSmoother", "LeftILU0", "RightILU0"]
+           "Chebyshev", "ChebyshevPreconditioner", "ChebyshevSmoother", "LeftILU0", "RightILU0",
+           "FSAI", "FSAIPreconditioner", "FSAIPreconditionerType"]

@@ -21,6 +21,9 @@ PSK_EXIT_NONE, PSK_EXIT_TOLERANCE, PSK_EXIT_ARNOLDI_BREAKDOWN, PSK_EXIT_MAXITER,
 PSK_HOST, PSK_DEVICE = 0, 1
 PSK_VCYCLE_X0_GIVEN = 1   # psk_vcycle flags: x holds the starting iterate
 PSK_PREC_IDENTITY, PSK_PREC_JACOBI, PSK_PREC_ILU, PSK_PREC_AMG, PSK_PREC_DENSE, PSK_PREC_CHEBYSHEV = 0, 1, 2, 3, 4, 5
+PSK_PREC_FSAI = 6
+PSK_FSAI_ROW_CAP = 64       # psk_csr_fsai: longest pattern row (lower part, diagonal included)
+PSK_FSAI_WAVE_ONLY = 1      # psk_csr_fsai flags: every row through the wave-per-row kernel
 PSK_LAYOUT_CSR, PSK_LAYOUT_SLICED, PSK_LAYOUT_SLICED_WIDE, PSK_LAYOUT_SLICED_DICT, PSK_LAYOUT_DIAG = 0, 1, 2, 3, 4
 PSK_UNIQUE_ID_BYTES = 128
 PSK_SPGEMM_ROW_CAP = 1024   # psk_csr_matmat: products of one output row
@@ -98,6 +101,9 @@ SIGNATURES = {
     "psk_sa_prolongator": (ctypes.c_int, [P, P, I64, P, F64, I32, PP]),
     "psk_csr_ilu0": (ctypes.c_int, [P, PP]),
     "psk_prec_create_ilu0": (ctypes.c_int, [P, PP]),
+    "psk_csr_fsai": (ctypes.c_int, [P, P, I32, PP, ctypes.POINTER(I32)]),
+    "psk_prec_create_fsai": (ctypes.c_int, [P, P, I32, PP]),
+    "psk_prec_fsai_info": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I64), ctypes.POINTER(I32)]),
     "psk_pcg": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_gmres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_bicgstab": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),

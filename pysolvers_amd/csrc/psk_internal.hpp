@@ -118,6 +118,7 @@ struct HaloPeer {
 
 struct DenseInverse;
 struct Chebyshev;
+struct Fsai;
 // largest dense coarse inverse (psk_prec_create_dense_inverse): 32768^2 doubles = 8.6 GB
 constexpr int64_t kDenseMaxN = 32768;
 
@@ -307,6 +308,7 @@ struct psk_prec {
     psk::AmgHierarchy *amg = nullptr;   // PSK_PREC_AMG
     psk::DenseInverse *dense = nullptr; // PSK_PREC_DENSE (dense.hip)
     psk::Chebyshev *cheb = nullptr;     // PSK_PREC_CHEBYSHEV (cheby.hip)
+    psk::Fsai *fsai = nullptr;          // PSK_PREC_FSAI (fsai.hip)
 };
 
 namespace psk {
@@ -927,6 +929,9 @@ int cheby_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);
 void cheby_free(Chebyshev *ch);
 // measurement: ms per step of `reps` back-to-back fused steps, and of the same step as four launches (cheby.hip)
 int cheby_ab(const psk_prec *M, const double *v, int reps, double *fused_ms, double *pieces_ms);
+int fsai_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);   // fsai.hip; out must not alias v
+void fsai_free(Fsai *f);
+int64_t fsai_nnz(const Fsai *f);   // entries of G (psk_prec_info)
 // measurement (ilu0.hip; the lab library reads it): host wall time of the phases of the last psk_csr_ilu0 /
 // psk_prec_create_ilu0 — the column sort and structure checks, the pattern download and dependency levels, the
 // numeric launches (HIP events), then for the preconditioner the value download and L / U split and
@@ -941,7 +946,7 @@ const Ilu0Timing &ilu0_last_timing();
 // Krylov drivers take their general path for these
 inline bool prec_is_general(const psk_prec *M) {
     return M && (M->kind == PSK_PREC_ILU || M->kind == PSK_PREC_AMG || M->kind == PSK_PREC_DENSE ||
-                 M->kind == PSK_PREC_CHEBYSHEV);
+                 M->kind == PSK_PREC_CHEBYSHEV || M->kind == PSK_PREC_FSAI);
 }
 // reports a bounded-spin timeout of any triangular solve inside M (syncs the stream)
 int prec_check_error(const psk_prec *M, hipStream_t s);
@@ -955,6 +960,13 @@ int csr_choose_layout(psk_csr *A, hipStream_t s);
 int csr_new_device(int64_t n, int64_t ncols, int64_t nnz, psk_csr **out);
 int csr_finish_device(psk_csr *A, hipStream_t s);
 void csr_discard(psk_csr *A);
+// exclusive scan of n int32 counts into rowptr[n + 1] on the device (spgemm.hip), in two steps so that the caller can
+// allocate by the total in between: exscan_total leaves the tile prefixes in tiles[exscan_tiles(n) + 1] and returns
+// the total on the host (syncs s), exscan_finish writes rowptr
+constexpr int kScanTile = 4 * kBlock;
+inline int64_t exscan_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
+int exscan_total(int64_t n, const int32_t *counts, int64_t *tiles, int64_t nt, hipStream_t s, int64_t *total);
+int exscan_finish(int64_t n, const int32_t *counts, const int64_t *tiles, int64_t nt, int32_t *rowptr, hipStream_t s);
 // one-shot SpMV (grid = tiles of A->tile_rows rows); dot modes write their grid sum to partial[0].
 // ev0/ev1 (optional): HIP events the dispatch itself records at the kernel's start and end
 // (hipExtLaunchKernel), so their interval is the kernel alone, without the launch gaps around it

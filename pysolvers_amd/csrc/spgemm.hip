@@ -44,7 +44,6 @@ namespace psk {
 
 constexpr int kSpgemmCap = 1024;    // products of one output row (documented in include/psk.h)
 constexpr int kSpgemmSmall = 256;   // rows up to here run in the small bin
-constexpr int kScanTile = 4 * kBlock;
 
 struct CsrView {
     int64_t m, ncols;
@@ -248,8 +247,9 @@ __global__ __launch_bounds__(kBlock) void scan_finish_kernel(int64_t n, const in
     if (blockIdx.x == 0 && threadIdx.x == 0) rowptr[n] = (int32_t)tile_sums[nt];
 }
 
-// counts[n] -> *total (host), leaving the tile prefixes in `tiles` for scan_finish
-static int scan_total(int64_t n, const int32_t *counts, int64_t *tiles, int64_t nt, hipStream_t s, int64_t *total) {
+// counts[n] -> *total (host), leaving the tile prefixes in `tiles` for exscan_finish
+// (declared in psk_internal.hpp: fsai.hip sizes its result the same way)
+int exscan_total(int64_t n, const int32_t *counts, int64_t *tiles, int64_t nt, hipStream_t s, int64_t *total) {
     if (nt > 0)
         hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)nt), dim3(kBlock), 0, s, n, counts, tiles);
     hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(kBlock), 0, s, nt, tiles);
@@ -258,7 +258,7 @@ static int scan_total(int64_t n, const int32_t *counts, int64_t *tiles, int64_t 
     PSK_HIP(hipStreamSynchronize(s));
     return PSK_OK;
 }
-static int scan_finish(int64_t n, const int32_t *counts, const int64_t *tiles, int64_t nt, int32_t *rowptr,
+int exscan_finish(int64_t n, const int32_t *counts, const int64_t *tiles, int64_t nt, int32_t *rowptr,
                        hipStream_t s) {
     if (nt > 0) {
         hipLaunchKernelGGL(scan_finish_kernel, dim3((unsigned)nt), dim3(kBlock), 0, s, n, counts, tiles, nt, rowptr);
@@ -301,11 +301,11 @@ static int matmat_views(const CsrView &A, const CsrView &B, psk_csr **out) {
         }
     }
     int64_t nnz = 0;
-    PSK_TRY(scan_total(m, counts, tiles, nt, s, &nnz));
+    PSK_TRY(exscan_total(m, counts, tiles, nt, s, &nnz));
     if (nnz > kMaxNnz) return fail(PSK_ERR_UNSUPPORTED, "psk_csr_matmat: the result exceeds the int32 nnz limit");
     psk_csr *C = nullptr;
     PSK_TRY(csr_new_device(m, B.ncols, nnz, &C));
-    int rc = scan_finish(m, counts, tiles, nt, C->rowptr, s);
+    int rc = exscan_finish(m, counts, tiles, nt, C->rowptr, s);
     if (rc == PSK_OK && m > 0) {
         hipLaunchKernelGGL((spgemm_row_kernel<kSpgemmSmall, true>), grid, dim3(kBlock), 0, s, A, B,
                            (int32_t *)nullptr, (const int32_t *)C->rowptr, C->colidx, C->vals, flag);
@@ -429,8 +429,8 @@ int psk_csr_transpose(const psk_csr *A, psk_csr **At) {
                                nnz, (const int32_t *)A->colidx, cnt);
         PSK_HIP(hipGetLastError());
         int64_t total = 0;
-        PSK_TRY(scan_total(nr, cnt, tiles, nt, s, &total));
-        PSK_TRY(scan_finish(nr, cnt, tiles, nt, T->rowptr, s));
+        PSK_TRY(exscan_total(nr, cnt, tiles, nt, s, &total));
+        PSK_TRY(exscan_finish(nr, cnt, tiles, nt, T->rowptr, s));
         if (nnz > 0) {
             hipLaunchKernelGGL(transpose_scatter_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                                m, (const int32_t *)A->rowptr, (const int32_t *)A->colidx, (const int32_t *)T->rowptr,
