@@ -42,6 +42,8 @@
  *   psk_csr_ilu0, psk_prec_create_ilu0: ILU(0) factored on the device; no reference counterpart (the
  *                    reference's incomplete factors are SuperLU's).
  *   psk_prec_trisolve_sweeps: opt-in approximate triangular applies by Jacobi sweeps; no reference counterpart.
+ *   psk_pcg_multi    several right-hand sides in one PCG loop, each column the recurrence of psk_pcg; no reference
+ *                    counterpart (the reference solves one vector per call).
  *   psk_csr_fsai, psk_prec_create_fsai: factorized sparse approximate inverse G ~ L^-1 formed on the device and
  *                    applied as two SpMVs; no reference counterpart.
  */
@@ -514,6 +516,40 @@ int psk_bicgstab(const psk_csr *A, const psk_prec *M, const double *b, double *x
  * PSK_ERR_UNSUPPORTED. */
 int psk_minres(const psk_csr *A, const psk_prec *M, const double *b, double *x, const psk_ctl *ctl,
                psk_result *res, double *hist, int32_t loc);
+/* PCG on 1 <= nrhs <= PSK_PCG_MULTI_MAX right-hand sides in ONE device loop (no reference counterpart: the reference
+ * solves one vector per call). The matrix is streamed once per iteration for all columns; the bound is the grid sum's
+ * width (one sum carries one dot product of every column).
+ * B and X are n x nrhs, row-major: element (i, j) at i*nrhs + j, a C-contiguous numpy (n, nrhs) array; with loc ==
+ * PSK_DEVICE B is read in place and X written once, at the end (X must not alias B: PSK_ERR_ARG). res points to nrhs
+ * results, res[j] column j's. hist: nullable HOST array of nrhs * ctl->maxiter doubles, column j's history from
+ * hist + j*maxiter; entries past res[j].hist_len are left untouched.
+ * EACH COLUMN IS AN INDEPENDENT PCG with the recurrence of psk_pcg (PCGSolver.py:97-138), x0 = 0, every elementwise
+ * operation rounded once (no contraction), every matrix row summed in stored order from 0.0 with the products
+ * rounded first (the bits of psk_spmv on that column):
+ *   r = b; u = M^-1 r; p = u; normB = sqrt(b.b); udr = u.r
+ *   k = 0, 1, ...: Ap = A p; alpha = udr / p.Ap; x = x + alpha p; r = r - alpha Ap; u = M^-1 r; hist[k] = sqrt(r.r);
+ *       hist[k] <= tau*normB, or k == maxiter-1 with !fail_on_maxiter: stop
+ *       beta = u.r / udr; udr = u.r; p = u + beta p
+ * Every dot product is a sum of products rounded one by one, one per row, in an order that depends on the tile and
+ * slot indices only: for a given nrhs a column's sums, and with them all its bits, do not depend on its position
+ * among the columns or on what the other columns hold, and two identical calls give identical bits. (The sums are
+ * not those of psk_pcg: iteration counts may differ from it where a residual lies within rounding of the threshold.)
+ * Each column has its own udr, alpha, beta, normB, threshold, history, iteration count, exit and breakdown, reported
+ * as psk_pcg reports them: stopping at iteration k is PSK_CONVERGED with iters = k+1, hist_len = k+1, resid =
+ * resid_recursive = hist[k], exit = PSK_EXIT_TOLERANCE (or PSK_EXIT_MAXITER by the maxiter rule); u.r == 0 at the
+ * start (b != 0) is PSK_BREAKDOWN with iters = 0, p.Ap == 0 at iteration k PSK_BREAKDOWN with iters = k, hist_len = k,
+ * resid = NaN, exit = PSK_EXIT_DOT_BREAKDOWN; maxiter reached is PSK_MAXITER with iters = maxiter-1, resid = the last
+ * hist; b_j = 0 is x_j = 0, PSK_CONVERGED, iters = 1, resid = 0, exit = PSK_EXIT_NONE, hist_len = 0. A breakdown stops
+ * that column only. A column that has stopped is frozen: later iterations write nothing to its x, r, p or hist (x_j is
+ * the iterate it stopped with). The loop ends when every column has stopped, or at maxiter.
+ * loop_ms, spmv_launches (launches of the multi-column SpMV that did their work) and, with ctl->time_kernels, spmv_ms
+ * are device-wide: the same in every res[j]. ctl->norm_b and ctl->restart are ignored.
+ * Preconditioners: M == NULL (identity) and PSK_PREC_JACOBI; any other kind is PSK_ERR_UNSUPPORTED, and so is a matrix
+ * sharded over more than one rank. nrhs outside 1 .. PSK_PCG_MULTI_MAX: PSK_ERR_ARG. The loop reads the matrix's CSR
+ * arrays whatever its SpMV layout (psk_csr_layout); it shares the matrix's solver workspace with the other solvers. */
+#define PSK_PCG_MULTI_MAX 4
+int psk_pcg_multi(const psk_csr *A, const psk_prec *M, int32_t nrhs, const double *B, double *X,
+                  const psk_ctl *ctl, psk_result *res /* nrhs of them */, double *hist, int32_t loc);
 /* The standalone AMG V-cycle solver, AMGVCycleSolver.solve (VCycleSolver.py:52-95), on the device: M is a
  * PSK_PREC_AMG whose finest level matrix is the system matrix (PSK_ERR_ARG otherwise); its own num_iters and
  * tau are ignored, ctl->maxiter (> 0) and ctl->tau rule. x0 = copy(b) (:69), or the caller's x with

@@ -91,7 +91,8 @@ int psk_lab_pcg_flush(int64_t n, int64_t k, int32_t stag, double *x, const doubl
  * large workspace, then those of its small one, each counted from its own buffer's start), bytes[2] = the sizes the two
  * buffers are grown to (the V-cycle has one: bytes[1] = 0). On entry *count = the capacity of offsets.
  * PCG reads n, ncols, maxiter, flags (GEN, OWN_X) and P ranks; GMRES n, maxiter, restart, flags (GEN); the V-cycle
- * n, maxiter, flags (DEV_IO); BiCGStab n, maxiter, flags (GEN); MINRES n, maxiter, flags (GEN).
+ * n, maxiter, flags (DEV_IO); BiCGStab n, maxiter, flags (GEN); MINRES n, maxiter, flags (GEN); the multi-column PCG
+ * (psk_pcg_multi) n, maxiter and P = nrhs (1 .. PSK_PCG_MULTI_MAX, PSK_ERR_ARG beyond).
  * Solver id 4 is not taken:
  * tests/test_solver_layout.py keeps it as its example of an unknown solver. */
 #define PSK_LAB_SOLVER_PCG 0
@@ -99,6 +100,7 @@ int psk_lab_pcg_flush(int64_t n, int64_t k, int32_t stag, double *x, const doubl
 #define PSK_LAB_SOLVER_VCYCLE 2
 #define PSK_LAB_SOLVER_BICGSTAB 3
 #define PSK_LAB_SOLVER_MINRES 5
+#define PSK_LAB_SOLVER_PCG_MULTI 6
 #define PSK_LAB_LAYOUT_GEN 1    /* general preconditioner (u, GMRES's w and t, or BiCGStab's ph and sh, materialised) */
 #define PSK_LAB_LAYOUT_OWN_X 2  /* PCG: x in the workspace (host vectors), not the caller's device vector */
 #define PSK_LAB_LAYOUT_DEV_IO 4 /* V-cycle: b and x are the caller's device vectors (not staged) */
@@ -140,6 +142,17 @@ int psk_lab_pcg_internals(const psk_csr *A, int64_t maxiter, int32_t gen, int32_
                           double *Ap, double *u, double *x, double *alphas, double *udr, double *hist, double *sums,
                           double *state);
 int psk_lab_pcg_prefill(psk_csr *A, int64_t maxiter, int32_t gen, int32_t own_x, int32_t byte);
+/* Tests of the multi-column PCG kernels (tests/test_gpu_pcg_multi.py): what the last psk_pcg_multi on matrix A left in
+ * its workspace, carved again for the same maxiter and nrhs; waits for the library stream and copies to host arrays,
+ * any of which may be NULL. With KP = nrhs rounded up to 2 or 4: alphas, udr and pap hold nrhs rows of maxiter + 1
+ * entries (alphas[j][k] and pap[j][k] = column j's alpha and p.Ap sum of iteration k, udr[j][k] its u.r in front of
+ * iteration k; entries of iterations the column did not run are left as the solve found them); r, p, Ap and x are the
+ * final INTERLEAVED work vectors, n x KP row-major (padding columns included); state holds 10 doubles per column:
+ * done (0 running, 1 converged or b = 0, 2 breakdown), brk_kind, iters, history entries, normB, tauNormB, the current
+ * udr, the last reported ||r||, the init's b.b sum and the last r.r sum the column took part in. PSK_ERR_ARG when
+ * either buffer is smaller than that layout needs, nrhs is out of range or the matrix is sharded. It reads only. */
+int psk_lab_pcg_multi_internals(const psk_csr *A, int64_t maxiter, int32_t nrhs, double *alphas, double *udr, double *pap,
+                                double *r, double *p, double *Ap, double *x, double *state);
 /* Measurement (tools/ilu0_ab.py): where the last psk_csr_ilu0 / psk_prec_create_ilu0 of this process spent its time.
  * out[0..6] = ms of the column sort and structure checks, of the pattern download and dependency levels, of the
  * numeric launches (HIP events around them), of the value download and L / U split, of psk_prec_create_trisolve

@@ -26,6 +26,7 @@ PSK_FSAI_ROW_CAP = 64       # psk_csr_fsai: longest pattern row (lower part, dia
 PSK_FSAI_WAVE_ONLY = 1      # psk_csr_fsai flags: every row through the wave-per-row kernel
 PSK_LAYOUT_CSR, PSK_LAYOUT_SLICED, PSK_LAYOUT_SLICED_WIDE, PSK_LAYOUT_SLICED_DICT, PSK_LAYOUT_DIAG = 0, 1, 2, 3, 4
 PSK_UNIQUE_ID_BYTES = 128
+PSK_PCG_MULTI_MAX = 4       # psk_pcg_multi: right-hand sides of one call
 PSK_SPGEMM_ROW_CAP = 1024   # psk_csr_matmat: products of one output row
 
 STATUS_NAMES = {PSK_CONVERGED: "converged", PSK_MAXITER: "maxiter", PSK_BREAKDOWN: "breakdown",
@@ -108,6 +109,7 @@ SIGNATURES = {
     "psk_gmres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_bicgstab": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_minres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
+    "psk_pcg_multi": (ctypes.c_int, [P, P, I32, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_vcycle": (ctypes.c_int, [P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32, I32]),
     "psk_comm_unique_id": (ctypes.c_int, [P]),
     "psk_comm_init": (ctypes.c_int, [I32, I32, P, PP]),
@@ -152,6 +154,7 @@ LAB_SIGNATURES = {
     "psk_lab_gmres_prefill": (ctypes.c_int, [P, I64, I32, I32, I32]),
     "psk_lab_pcg_internals": (ctypes.c_int, [P, I64, I32, I32, P, P, P, P, P, P, P, P, P, P]),
     "psk_lab_pcg_prefill": (ctypes.c_int, [P, I64, I32, I32, I32]),
+    "psk_lab_pcg_multi_internals": (ctypes.c_int, [P, I64, I32, P, P, P, P, P, P, P, P]),
     "psk_lab_ilu0_timing": (ctypes.c_int, [ctypes.POINTER(F64)]),
 }
 _lab = None

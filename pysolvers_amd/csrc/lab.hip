@@ -453,11 +453,40 @@ extern "C" int psk_lab_solver_layout(int32_t solver, int64_t n, int64_t ncols, i
     else if (solver == PSK_LAB_SOLVER_GMRES) gmres_layout_probe(n, maxiter, restart, gen, &log, bytes);
     else if (solver == PSK_LAB_SOLVER_BICGSTAB) bicgstab_layout_probe(n, maxiter, gen, &log, bytes);
     else if (solver == PSK_LAB_SOLVER_MINRES) minres_layout_probe(n, maxiter, gen, &log, bytes);
+    else if (solver == PSK_LAB_SOLVER_PCG_MULTI && P <= PSK_PCG_MULTI_MAX) pcg_multi_layout_probe(n, maxiter, P, &log, bytes);
     else if (solver == PSK_LAB_SOLVER_VCYCLE) vcycle_layout_probe(n, maxiter, (flags & PSK_LAB_LAYOUT_DEV_IO) != 0, &log, bytes);
     else return fail(PSK_ERR_ARG, "psk_lab_solver_layout: unknown solver");
     if ((size_t)*count < log.size()) return fail(PSK_ERR_ARG, "psk_lab_solver_layout: offsets too short");
     *count = (int32_t)log.size();
     for (size_t i = 0; i < log.size(); ++i) offsets[i] = log[i];
+    return PSK_OK;
+}
+
+// ---- psk_pcg_multi's workspace after a solve (pcg_multi.hip pcg_multi_work_view) ----
+extern "C" int psk_lab_pcg_multi_internals(const psk_csr *A, int64_t maxiter, int32_t nrhs, double *alphas, double *udr,
+                                           double *pap, double *r, double *p, double *Ap, double *x, double *state) {
+    using namespace psk;
+    if (!A || A->comm) return fail(PSK_ERR_ARG, "psk_lab_pcg_multi_internals: bad arguments");
+    PcgMultiView v;
+    PSK_TRY(pcg_multi_work_view(const_cast<psk_csr *>(A), maxiter, nrhs, &v));
+    Context *c;
+    PSK_TRY(ctx(&c));
+    PSK_HIP(hipStreamSynchronize(c->stream));
+    const size_t vec = (size_t)v.n * (size_t)v.kp * 8, it = (size_t)v.ld * 8;
+    const struct {
+        double *dst;
+        const double *src;
+    } vecs[4] = {{r, v.r}, {p, v.p}, {Ap, v.Ap}, {x, v.x}}, its[3] = {{alphas, v.alphas}, {udr, v.udrs}, {pap, v.paps}};
+    for (const auto &q : vecs)
+        if (q.dst && vec) PSK_HIP(hipMemcpy(q.dst, q.src, vec, hipMemcpyDeviceToHost));
+    for (const auto &q : its)
+        for (int j = 0; q.dst && j < nrhs; ++j)
+            PSK_HIP(hipMemcpy(q.dst + (size_t)j * (size_t)v.ld, q.src + (size_t)j * (size_t)v.ld, it, hipMemcpyDeviceToHost));
+    if (state) {
+        std::vector<char> hs(pcg_multi_state_bytes());
+        PSK_HIP(hipMemcpy(hs.data(), v.state, hs.size(), hipMemcpyDeviceToHost));
+        for (int j = 0; j < nrhs; ++j) pcg_multi_col_state(hs.data(), j, state + (size_t)j * kMultiStateWords);
+    }
     return PSK_OK;
 }
 

@@ -447,7 +447,7 @@ constexpr int64_t kGridSumL = (int64_t)1 << kGridSumLLog;   // groups interleave
 // at 16384^2)
 constexpr int kGridSumCntStride = 64;
 constexpr uint64_t kGridSumSentinel = 0x7FF0000000000001ull;   // sNaN: arithmetic never produces it
-constexpr int kGridSumMaxW = 4;
+constexpr int kGridSumMaxW = 8;   // psk_pcg_multi's U: [r.r, u.r] of four columns (sizes the armed group-sum slots only)
 constexpr int64_t kGridSumMaxGroups = kMaxGrid;
 // a wait on an already-issued store that has not landed after ~1.3 s (s_memrealtime, 100 MHz) is
 // reported (gridsum_check) instead of hanging the launch: never expected

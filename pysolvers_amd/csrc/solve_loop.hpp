@@ -30,6 +30,7 @@ void gmres_layout_probe(int64_t n, int64_t maxiter, int64_t restart, bool gen, s
 void bicgstab_layout_probe(int64_t n, int64_t maxiter, bool gen, std::vector<int64_t> *log, int64_t *bytes);
 void minres_layout_probe(int64_t n, int64_t maxiter, bool gen, std::vector<int64_t> *log, int64_t *bytes);
 void vcycle_layout_probe(int64_t n, int64_t maxiter, bool dev_io, std::vector<int64_t> *log, int64_t *bytes);
+void pcg_multi_layout_probe(int64_t n, int64_t maxiter, int nrhs, std::vector<int64_t> *log, int64_t *bytes);
 
 // ---- what every solver writes into its psk_result the same way (res was zeroed by the entry point) ----
 inline void result_msg(psk_result *res, const char *m) { std::snprintf(res->msg, sizeof(res->msg), "%s", m); }
@@ -58,6 +59,23 @@ struct GmresView {
     size_t big_bytes, small_bytes;
 };
 int gmres_work_view(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool grow, GmresView *v);
+
+// psk_pcg_multi's workspace as the lab library reads it after a solve (pcg_multi.hip pcg_multi_work_view): device
+// pointers into the matrix's two buffers. x, r, p, Ap: n rows of kp interleaved columns; alphas, udrs, paps: kp rows
+// of ld = maxiter + 1 entries; state: the solve's device state, pcg_multi_state_bytes() of it, decoded column by
+// column by pcg_multi_col_state into kMultiStateWords doubles (done, brk_kind, iters, nhist, normB, tauNormB, udr,
+// the last reported ||r||, the init's b.b, the column's last r.r).
+struct PcgMultiView {
+    int64_t n;
+    int kp;
+    int64_t ld;
+    double *x, *r, *p, *Ap, *alphas, *udrs, *paps;
+    const void *state;
+};
+constexpr int kMultiStateWords = 10;
+int pcg_multi_work_view(psk_csr *A, int64_t maxiter, int nrhs, PcgMultiView *v);
+size_t pcg_multi_state_bytes();
+void pcg_multi_col_state(const void *state, int j, double *out);
 
 // The done stamp (done_stamp_store, called by the kernel of each solver that ends its loop): k + 2 for a kernel of
 // iteration k (psk_gmres: step k of the current cycle), 1 for the init (0 = running) — a system-scope store to a
