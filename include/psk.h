@@ -46,6 +46,8 @@
  *                    counterpart (the reference solves one vector per call).
  *   psk_csr_fsai, psk_prec_create_fsai: factorized sparse approximate inverse G ~ L^-1 formed on the device and
  *                    applied as two SpMVs; no reference counterpart.
+ *   psk_color_plan, psk_prec_create_mcgs: Gauss-Seidel in a colour ordering, one streaming launch per colour; no
+ *                    reference counterpart (the reference's Gauss-Seidel smoother is spsolve(triu(A), .)).
  */
 #ifndef PSK_H
 #define PSK_H
@@ -454,6 +456,48 @@ int psk_prec_create_fsai(const psk_csr *A, const psk_csr *pattern, int32_t flags
 /* The formed factor: A's sign, the entries of G and its longest row. Any out pointer may be NULL. PSK_ERR_ARG when M
  * is not a PSK_PREC_FSAI. */
 int psk_prec_fsai_info(const psk_prec *M, int32_t *sign, int64_t *nnz_g, int32_t *max_row);
+
+/* ---- multicolour Gauss-Seidel (color_plan.hip, mcgs.hip) ---------------------------------------- */
+/* A colouring of the n rows of a square CSR structure (host arrays; no device is touched): first-fit greedy in natural
+ * row order on the structure of A + A^T. The neighbours of row i are the columns j != i stored in row i plus the rows
+ * j != i that store column i; explicitly stored zeros count as structure; rows may be unsorted and hold duplicate
+ * columns. For i = 0..n-1 ascending, color[i] = the smallest c >= 0 that no already-coloured neighbour holds;
+ * *ncolors = max(color) + 1. No two neighbours share a colour. O(nnz) (A^T's structure by a counting sort). Exactly
+ * red/black on the 5-point stencil. PSK_ERR_ARG: n <= 0, a column outside [0, n), row pointers that do not start at 0 or that decrease. Replaces
+ * nothing in the reference. */
+int psk_color_plan(int64_t n, const int32_t *rowptr, const int32_t *colidx, int32_t *color, int32_t *ncolors);
+/* The multicolour Gauss-Seidel preconditioner of a square device CSR A: z = M^-1 v is `sweeps` Gauss-Seidel sweeps
+ * for A z = v from z = 0 with the rows ordered by the colours of psk_color_plan, C of them. Rows of one colour do not
+ * reference each other, so each colour is one streaming launch: no dependency level, no wait between workgroups, no
+ * grid sum, and a sweep over all colours reads A once.
+ * Setup: A's structure is coloured on the host; more than PSK_MCGS_MAX_COLORS colours is PSK_ERR_UNSUPPORTED
+ * (psk_last_error names the count). The preconditioner owns a colour-grouped copy of A (colour 0's rows first, ascending
+ * row index inside a colour, every row's entries in their stored order) and DInv_i = 1.0 / a_ii, a_ii = the sum of row
+ * i's stored col == row entries in stored order as for PSK_PREC_JACOBI; a diagonal that is zero, missing or not
+ * finite is PSK_ERR_ARG (psk_last_error names the smallest such row). A is not borrowed.
+ * Apply, all f64, every operation rounded once, a product rounded before its add (no FMA):
+ *   z = 0
+ *   repeat `sweeps` times: for colour k in ORDER, for every row i of colour k independently:
+ *       acc = 0.0;  acc = acc + a_ij * z_j for every stored entry of row i, diagonal included, in stored order
+ *       z_i = z_i + DInv_i * (v_i - acc)
+ * ORDER = 0, 1, ..., C-1; with PSK_MCGS_SYMMETRIC, 0, ..., C-1, C-2, ..., 0 (2C-1 launches; repeating colour C-1
+ * would change nothing in exact arithmetic). A launch reads z_j of other colours and writes only its own rows' z_i, so
+ * the result does not depend on the launch geometry. out must not alias v.
+ * With PSK_MCGS_SYMMETRIC and a symmetric positive definite A the operator is symmetric positive definite for any
+ * sweeps >= 1: it is (I - (I - M_sgs^-1 A)^sweeps) A^-1 with M_sgs the symmetric Gauss-Seidel splitting in the colour
+ * order. PCG and MINRES take it with the flag; GMRES, BiCGStab and the smoother[k] slot of psk_prec_create_amg take
+ * either form (as a smoother, x <- x + M^-1 (f - A x) with sweeps = 1 is one Gauss-Seidel sweep from x in the
+ * colour order). psk_pcg_multi answers PSK_ERR_UNSUPPORTED for it.
+ * psk_prec_info reports kind PSK_PREC_MCGS, nnz_l = nnz_u = nnz(A) and levels_l = levels_u = C.
+ * PSK_ERR_ARG also: sweeps < 1, an unknown flag, A not square or empty. PSK_ERR_UNSUPPORTED also: a sharded A.
+ * Replaces nothing in the reference. */
+#define PSK_PREC_MCGS        7     /* preconditioner kind: multicolour Gauss-Seidel (psk_prec_create_mcgs) */
+#define PSK_MCGS_MAX_COLORS  64    /* most colours a matrix may need */
+#define PSK_MCGS_SYMMETRIC   1     /* flags: colours forward then backward (symmetric Gauss-Seidel) */
+int psk_prec_create_mcgs(const psk_csr *A, int32_t sweeps, int32_t flags, psk_prec **out);
+/* What was formed: the colour count, the sweeps, the flags and the rows of each colour (color_rows: *ncolors counts, at
+ * most PSK_MCGS_MAX_COLORS). Any out pointer may be NULL. PSK_ERR_ARG when M is not a PSK_PREC_MCGS. */
+int psk_prec_mcgs_info(const psk_prec *M, int32_t *ncolors, int32_t *sweeps, int32_t *flags, int64_t *color_rows);
 
 /* ---- solvers ------------------------------------------------------------------------------ */
 /* M == NULL means identity. b, x: length n (local length for a distributed A); with loc ==

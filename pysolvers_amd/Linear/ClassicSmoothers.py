@@ -4,6 +4,7 @@ Both of the reference's smoothers are a sweep x <- x + S^-1 (f - A x):
 * JacobiSmoother      S^-1 r = DInv * r, DInv = reciprocal(diag A)      (:5-14)
 * GaussSeidelSmoother S^-1 r = spsolve(triu(A), r)                      (:28-36)
 * ChebyshevSmoother   S^-1 r = p(D^-1 A) D^-1 r, p the Chebyshev polynomial of a degree (no reference counterpart)
+* MulticolorGaussSeidelSmoother S^-1 r = Gauss-Seidel sweeps from 0 in a colour ordering (no reference counterpart)
 Each class builds that S^-1 as a device operator (``.operator``); the V-cycle itself runs inside
 libpsk (psk_prec_create_amg). ``apply(f, x, nu)`` keeps the reference's host-callable contract.
 """
@@ -11,7 +12,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from .DeviceMatrix import DeviceCSR, spmv
-from .Preconditioner import ChebyshevPreconditioner, JacobiPreconditioner
+from .Preconditioner import ChebyshevPreconditioner, JacobiPreconditioner, MulticolorGSPreconditioner
 from .TriangularSolve import TriangularSolveChain
 
 
@@ -64,3 +65,23 @@ class ChebyshevSmoother(_Smoother):
         Gershgorin bound) unless the levels share a bound."""
         name = "ChebyshevSmoother_d%d" % int(degree)
         return type(name, (cls,), dict(degree=int(degree), ratio=float(ratio), lmax=lmax))
+
+
+class MulticolorGaussSeidelSmoother(_Smoother):
+    """S^-1 r = Gauss-Seidel sweeps for A z = r from z = 0 in a colour ordering (MulticolorGSPreconditioner on the
+    level's device matrix), so the smoother sweep x <- x + S^-1 (f - A x) with one sweep is a Gauss-Seidel sweep from
+    x in the colour order: one streaming launch per colour instead of the triangular solve of GaussSeidelSmoother.
+    No reference counterpart. The class itself means one symmetric sweep; ``MulticolorGaussSeidelSmoother.of(...)``
+    gives a configured subclass (``smoother=`` takes a class)."""
+
+    sweeps, symmetric = 1, True
+
+    def __init__(self, A, device_A=None):
+        super().__init__(A, device_A)
+        self.operator = MulticolorGSPreconditioner(self._dA, sweeps=self.sweeps, symmetric=self.symmetric)
+
+    @classmethod
+    def of(cls, sweeps=1, symmetric=True):
+        """A subclass with these settings."""
+        name = "MulticolorGaussSeidelSmoother_s%d%s" % (int(sweeps), "" if symmetric else "_fwd")
+        return type(name, (cls,), dict(sweeps=int(sweeps), symmetric=bool(symmetric)))

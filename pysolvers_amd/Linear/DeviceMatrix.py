@@ -199,6 +199,18 @@ class DeviceCSR:
                                    ctypes.byref(sign)), "psk_csr_fsai")
         return DeviceCSR._adopt(h, self.ncols), sign.value
 
+    def coloring(self):
+        """``(color, ncolors)``: the colouring of this square matrix's rows that the multicolour Gauss-Seidel
+        preconditioner uses (psk_color_plan on the downloaded structure: first-fit greedy in natural row order on the
+        structure of A + A^T; host code). ``color`` is an int32 array of n colours."""
+        indptr = np.empty(self.n + 1, dtype=np.int32)
+        indices = np.empty(max(self.nnz, 1), dtype=np.int32)
+        N.check(N.lib.psk_csr_download(self._h, N.ptr(indptr), N.ptr(indices), None), "psk_csr_download")
+        color, nc = np.empty(self.n, dtype=np.int32), N.I32()
+        N.check(N.lib.psk_color_plan(self.n, N.ptr(indptr), N.ptr(indices), N.ptr(color), ctypes.byref(nc)),
+                "psk_color_plan")
+        return color, nc.value
+
     def to_scipy(self):
         indptr = np.empty(self.n + 1, dtype=np.int32)
         indices = np.empty(self.nnz, dtype=np.int32)

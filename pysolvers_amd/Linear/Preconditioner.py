@@ -234,3 +234,48 @@ class FSAIPreconditioner(DeviceOperator, GenericPreconditioner):
 
     def apply(self, vec):
         return self._device_apply(vec)
+
+
+class MulticolorGSPreconditioner(DeviceOperator, GenericPreconditioner):
+    """M^-1 v = ``sweeps`` Gauss-Seidel sweeps for A z = v from z = 0 in a colour ordering of the rows
+    (psk_prec_create_mcgs, pysolvers_amd/csrc/mcgs.hip; the colouring is psk_color_plan's, first-fit greedy on the
+    structure of A + A^T).
+
+    No reference counterpart (the reference's Gauss-Seidel is spsolve(triu(A), .), ClassicSmoothers.py:28-36): rows of
+    one colour do not reference each other, so a colour updates in one streaming launch, with no dependency level,
+    no spin wait and no grid sum; a sweep reads A once. ``symmetric=True`` runs the colours forward then backward
+    (symmetric Gauss-Seidel, 2C-1 launches per sweep): the operator is then symmetric positive definite for an SPD A,
+    so PCG and MINRES may use it. ``symmetric=False`` is the forward sweep alone (GMRES, BiCGStab, AMG smoothing). A
+    matrix that needs more than PSK_MCGS_MAX_COLORS colours, or has a zero, missing or non-finite diagonal entry,
+    raises PskError. The arithmetic is stated to the bit in include/psk.h.
+    """
+
+    device_kind = N.PSK_PREC_MCGS
+
+    def __init__(self, A, sweeps=1, symmetric=True):
+        dA = as_device_matrix(A)             # read during the setup only: the handle owns a grouped copy
+        h = ctypes.c_void_p()
+        flags = N.PSK_MCGS_SYMMETRIC if symmetric else 0
+        N.check(N.lib.psk_prec_create_mcgs(dA.handle, int(sweeps), flags, ctypes.byref(h)), "psk_prec_create_mcgs")
+        self._h = h
+        self.n = dA.n
+        self.sweeps = int(sweeps)
+        self.symmetric = bool(symmetric)
+
+    @property
+    def ncolors(self):
+        """Colours of the ordering (2 on the 5-point stencil)."""
+        c = N.I32()
+        N.check(N.lib.psk_prec_mcgs_info(self._h, ctypes.byref(c), None, None, None), "psk_prec_mcgs_info")
+        return c.value
+
+    @property
+    def color_rows(self):
+        """Rows of each colour: ``ncolors`` counts (int64)."""
+        rows = np.zeros(N.PSK_MCGS_MAX_COLORS, dtype=np.int64)
+        c = N.I32()
+        N.check(N.lib.psk_prec_mcgs_info(self._h, ctypes.byref(c), None, None, N.ptr(rows)), "psk_prec_mcgs_info")
+        return rows[:c.value].copy()
+
+    def apply(self, vec):
+        return self._device_apply(vec)

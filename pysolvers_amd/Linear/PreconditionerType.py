@@ -2,7 +2,7 @@
 from abc import ABC, abstractmethod
 
 from .Preconditioner import (ChebyshevPreconditioner, FSAIPreconditioner, IdentityPreconditioner,
-                             JacobiPreconditioner)
+                             JacobiPreconditioner, MulticolorGSPreconditioner)
 
 
 class PreconditionerType(ABC):
@@ -56,3 +56,17 @@ class FSAIPreconditionerType(PreconditionerType):
 
 
 FSAI = FSAIPreconditionerType
+
+
+class MulticolorGSPreconditionerType(PreconditionerType):
+    """Gauss-Seidel sweeps in a colour ordering (MulticolorGSPreconditioner); ``symmetric=True`` for PCG / MINRES."""
+
+    def __init__(self, sweeps=1, symmetric=True):
+        self.sweeps = sweeps
+        self.symmetric = symmetric
+
+    def form(self, A):
+        return MulticolorGSPreconditioner(A, sweeps=self.sweeps, symmetric=self.symmetric)
+
+
+MulticolorGS = MulticolorGSPreconditionerType

@@ -9,11 +9,15 @@ from .Linear import (AMG, AMGVCycle, AMGVCycleSolver, BiCGStab, BiCGStabSolver, 
                      IdentityPreconditionerType, IterativeLinearSolver, Jacobi, JacobiPreconditioner,
                      JacobiPreconditionerType, LeftILUT, PCGSolver, RightILUT, mvmult,
                      Chebyshev, ChebyshevPreconditioner, ChebyshevSmoother, LeftILU0, RightILU0,
-                     FSAI, FSAIPreconditioner, FSAIPreconditionerType)
+                     FSAI, FSAIPreconditioner, FSAIPreconditionerType,
+                     MulticolorGS, MulticolorGSPreconditioner, MulticolorGSPreconditionerType,
+                     MulticolorGaussSeidelSmoother)
 
 __all__ = ["Nonlinear", "AMG", "AMGVCycle", "AMGVCycleSolver", "BiCGStab", "BiCGStabSolver", "MINRES", "MINRESSolver", "DefaultDirect", "RightIC", "GaussSeidelSmoother", "JacobiSmoother", "Linear", "CommonSolverArgs", "IterativeSolver", "NamedObject", "SolveStatus", "GMRES", "PCG",
            "GMRESSolver", "PCGSolver", "DeviceCSR", "DeviceVector", "IdentityPreconditioner",
            "IdentityPreconditionerType", "IterativeLinearSolver", "Jacobi", "JacobiPreconditioner",
            "JacobiPreconditionerType", "LeftILUT", "RightILUT", "mvmult",
            "Chebyshev", "ChebyshevPreconditioner", "ChebyshevSmoother", "LeftILU0", "RightILU0",
-           "FSAI", "FSAIPreconditioner", "FSAIPreconditionerType"]
+           "FSAI", "FSAIPreconditioner", "FSAIPreconditionerType",
+           "MulticolorGS", "MulticolorGSPreconditioner", "MulticolorGSPreconditionerType",
+           "MulticolorGaussSeidelSmoother"]

@@ -24,6 +24,9 @@ PSK_PREC_IDENTITY, PSK_PREC_JACOBI, PSK_PREC_ILU, PSK_PREC_AMG, PSK_PREC_DENSE, 
 PSK_PREC_FSAI = 6
 PSK_FSAI_ROW_CAP = 64       # psk_csr_fsai: longest pattern row (lower part, diagonal included)
 PSK_FSAI_WAVE_ONLY = 1      # psk_csr_fsai flags: every row through the wave-per-row kernel
+PSK_PREC_MCGS = 7
+PSK_MCGS_MAX_COLORS = 64    # psk_prec_create_mcgs: most colours a matrix may need
+PSK_MCGS_SYMMETRIC = 1      # psk_prec_create_mcgs flags: colours forward then backward
 PSK_LAYOUT_CSR, PSK_LAYOUT_SLICED, PSK_LAYOUT_SLICED_WIDE, PSK_LAYOUT_SLICED_DICT, PSK_LAYOUT_DIAG = 0, 1, 2, 3, 4
 PSK_UNIQUE_ID_BYTES = 128
 PSK_PCG_MULTI_MAX = 4       # psk_pcg_multi: right-hand sides of one call
@@ -105,6 +108,9 @@ SIGNATURES = {
     "psk_csr_fsai": (ctypes.c_int, [P, P, I32, PP, ctypes.POINTER(I32)]),
     "psk_prec_create_fsai": (ctypes.c_int, [P, P, I32, PP]),
     "psk_prec_fsai_info": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I64), ctypes.POINTER(I32)]),
+    "psk_color_plan": (ctypes.c_int, [I64, P, P, P, ctypes.POINTER(I32)]),
+    "psk_prec_create_mcgs": (ctypes.c_int, [P, I32, I32, PP]),
+    "psk_prec_mcgs_info": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32), P]),
     "psk_pcg": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_gmres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_bicgstab": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),

@@ -40,6 +40,7 @@ int prec_apply_dev(const psk_prec *M, int64_t n, const double *v, double *out, h
     if (M->kind == PSK_PREC_DENSE) return dense_apply(M, v, out, s);
     if (M->kind == PSK_PREC_CHEBYSHEV) return cheby_apply(M, v, out, s);
     if (M->kind == PSK_PREC_FSAI) return fsai_apply(M, v, out, s);
+    if (M->kind == PSK_PREC_MCGS) return mcgs_apply(M, v, out, s);
     return fail(PSK_ERR_UNSUPPORTED, "unknown preconditioner kind");
 }
 
@@ -161,6 +162,7 @@ int psk_prec_destroy(psk_prec *M) {
     if (M->dense) dense_free(M->dense);
     if (M->cheb) cheby_free(M->cheb);
     if (M->fsai) fsai_free(M->fsai);
+    if (M->mcgs) mcgs_free(M->mcgs);
     delete M;
     return PSK_OK;
 }
@@ -170,11 +172,13 @@ int psk_prec_info(const psk_prec *M, int32_t *kind, int64_t *n, int64_t *nnz_l, 
     if (!M) return fail(PSK_ERR_ARG, "psk_prec_info: NULL preconditioner");
     if (kind) *kind = M->kind;
     if (n) *n = M->n;
-    // FSAI: both "factors" are G (G and its transpose)
-    if (nnz_l) *nnz_l = M->fsai ? fsai_nnz(M->fsai) : M->lo.nnz;
-    if (nnz_u) *nnz_u = M->fsai ? fsai_nnz(M->fsai) : M->up.nnz;
-    if (levels_l) *levels_l = M->lo.levels;
-    if (levels_u) *levels_u = M->up.levels;
+    // FSAI: both "factors" are G (G and its transpose); multicolour Gauss-Seidel: the grouped copy of A, and its
+    // colours as the levels
+    const int64_t own = M->fsai ? fsai_nnz(M->fsai) : M->mcgs ? mcgs_nnz(M->mcgs) : -1;
+    if (nnz_l) *nnz_l = own >= 0 ? own : M->lo.nnz;
+    if (nnz_u) *nnz_u = own >= 0 ? own : M->up.nnz;
+    if (levels_l) *levels_l = M->mcgs ? mcgs_ncolors(M->mcgs) : M->lo.levels;
+    if (levels_u) *levels_u = M->mcgs ? mcgs_ncolors(M->mcgs) : M->up.levels;
     return PSK_OK;
 }
 

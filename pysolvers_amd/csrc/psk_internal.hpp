@@ -119,6 +119,7 @@ struct HaloPeer {
 struct DenseInverse;
 struct Chebyshev;
 struct Fsai;
+struct Mcgs;
 // largest dense coarse inverse (psk_prec_create_dense_inverse): 32768^2 doubles = 8.6 GB
 constexpr int64_t kDenseMaxN = 32768;
 
@@ -309,6 +310,7 @@ struct psk_prec {
     psk::DenseInverse *dense = nullptr; // PSK_PREC_DENSE (dense.hip)
     psk::Chebyshev *cheb = nullptr;     // PSK_PREC_CHEBYSHEV (cheby.hip)
     psk::Fsai *fsai = nullptr;          // PSK_PREC_FSAI (fsai.hip)
+    psk::Mcgs *mcgs = nullptr;          // PSK_PREC_MCGS (mcgs.hip)
 };
 
 namespace psk {
@@ -932,6 +934,10 @@ int cheby_ab(const psk_prec *M, const double *v, int reps, double *fused_ms, dou
 int fsai_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);   // fsai.hip; out must not alias v
 void fsai_free(Fsai *f);
 int64_t fsai_nnz(const Fsai *f);   // entries of G (psk_prec_info)
+int mcgs_apply(const psk_prec *M, const double *v, double *out, hipStream_t s);   // mcgs.hip; out must not alias v
+void mcgs_free(Mcgs *m);
+int64_t mcgs_nnz(const Mcgs *m);       // entries of the colour-grouped copy = nnz(A) (psk_prec_info)
+int64_t mcgs_ncolors(const Mcgs *m);   // psk_prec_info's levels
 // measurement (ilu0.hip; the lab library reads it): host wall time of the phases of the last psk_csr_ilu0 /
 // psk_prec_create_ilu0 — the column sort and structure checks, the pattern download and dependency levels, the
 // numeric launches (HIP events), then for the preconditioner the value download and L / U split and
@@ -946,7 +952,7 @@ const Ilu0Timing &ilu0_last_timing();
 // Krylov drivers take their general path for these
 inline bool prec_is_general(const psk_prec *M) {
     return M && (M->kind == PSK_PREC_ILU || M->kind == PSK_PREC_AMG || M->kind == PSK_PREC_DENSE ||
-                 M->kind == PSK_PREC_CHEBYSHEV || M->kind == PSK_PREC_FSAI);
+                 M->kind == PSK_PREC_CHEBYSHEV || M->kind == PSK_PREC_FSAI || M->kind == PSK_PREC_MCGS);
 }
 // reports a bounded-spin timeout of any triangular solve inside M (syncs the stream)
 int prec_check_error(const psk_prec *M, hipStream_t s);
