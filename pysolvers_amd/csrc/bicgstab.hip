@@ -335,38 +335,19 @@ static void bicg_layout(Carve &big, Carve &sm, int64_t n, int64_t maxiter, bool 
     w.hist = sm.take<double>((size_t)(maxiter + 1) * 8);
 }
 void bicgstab_layout_probe(int64_t n, int64_t maxiter, bool gen, std::vector<int64_t> *log, int64_t *bytes) {
-    Carve big, sm;
-    big.log = sm.log = log;
     BicgWork w;
-    bicg_layout(big, sm, n, maxiter, gen, w);
-    bytes[0] = big.off > 0 ? (int64_t)big.off : 256;
-    bytes[1] = (int64_t)sm.off;
+    layout_sizes([&](Carve &big, Carve &sm) { bicg_layout(big, sm, n, maxiter, gen, w); }, kWsFloor, log, bytes);
 }
 
 // what the phases of one solve share
-struct BicgRun {
-    psk_csr *A;
-    const psk_prec *M;
-    const psk_ctl *ctl;
-    Context *c;
-    SolveKit *kit;
-    hipStream_t s;
-    int64_t n, nv;
-    int C;           // iterations per poll chunk
-    bool gen;
-    const double *dinv;
+struct BicgRun : SolveRun {
     BicgWork w;
     GridSum gsB, gsD, gsE;
 };
 
 static int bicg_workspace(BicgRun &r) {
-    int64_t need[2];
-    bicgstab_layout_probe(r.n, r.ctl->maxiter, r.gen, nullptr, need);
-    PSK_TRY(r.A->ws.ensure((size_t)need[0]));
-    PSK_TRY(r.A->ws_small.ensure((size_t)need[1]));
-    Carve big{r.A->ws.as<char>()}, sm{r.A->ws_small.as<char>()};
-    bicg_layout(big, sm, r.n, r.ctl->maxiter, r.gen, r.w);
-    return PSK_OK;
+    auto layout = [&](Carve &big, Carve &sm) { bicg_layout(big, sm, r.n, r.ctl->maxiter, r.gen, r.w); };
+    return workspace_carve(r.A, kWsFloor, true, layout, nullptr);
 }
 
 // everything in front of the loop: the gridsums, the state, b, x0 = 0 and the init launch (b.b). *run: iterations
@@ -465,13 +446,7 @@ static int bicg_finish(BicgRun &r, BicgState *hs, double *true_sq, psk_result *r
         PSK_TRY(launch_spmv(r.A, kSpmvResid, w.x, w.t, nullptr, w.bv, w.sums + kBicgTrue, nullptr, s));
         PSK_HIP(hipMemcpyAsync(true_sq, w.sums + kBicgTrue, 8, hipMemcpyDeviceToHost, s));
     }
-    PSK_HIP(hipEventRecord(r.kit->ev1, s));
-    PSK_HIP(hipStreamSynchronize(s));
-    // an expired in-launch reduction wait poisons a sum with NaN; report it as the error it is
-    PSK_TRY(gridsum_check(r.c));
-    if (r.gen) PSK_TRY(prec_check_error(r.M, s));
-    res->loop_ms = loop_ms(r.kit);
-    return PSK_OK;
+    return solve_finish(r, res);
 }
 
 // SpMV launches of the loop that did their work (those enqueued behind `done` returned at once)
@@ -485,56 +460,16 @@ static int64_t bicg_spmv_count(const BicgState &hs, int64_t launched) {
 // The state hs of a finished loop that enqueued `launched` iterations, decoded into res; the history and x.
 static int bicg_report(const BicgRun &r, const BicgState &hs, int64_t launched, double true_sq, psk_result *res,
                        double *hist, double *xout, int32_t loc) {
-    const int64_t maxiter = r.ctl->maxiter;
     res->norm_b = hs.normB;
     res->spmv_launches = bicg_spmv_count(hs, launched) + (bicg_tol_exit(hs) ? 1 : 0);   // + the true residual's
     res->resid_recursive = hs.rec;
-    int64_t nh = hs.nhist;
-    if (hs.zero_b) {   // b = 0: x = 0 and resid = 0, as psk_pcg reports it
-        result_trivial(res);
-        nh = 0;
-    } else if (hs.done == 1) {
-        res->iters = hs.iters + 1;
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-        res->resid = hs.rec;
-        res->exit = hs.by_tol ? PSK_EXIT_TOLERANCE : PSK_EXIT_MAXITER;
-        if (bicg_tol_exit(hs)) {
-            const double tr = std::sqrt(true_sq);
-            res->resid = tr;
-            if (!(tr <= hs.tauNormB)) {
-                res->status = PSK_TRUE_RESID_FAIL;
-                res->success = 0;
-                std::snprintf(res->msg, sizeof(res->msg),
-                              "BiCGStab failure: true residual %12.5g did not meet tolerance tau=%12.5g. "
-                              "Recursive residual was %12.5g.",
-                              tr, r.ctl->tau, hs.rec);
-            }
-        }
-    } else if (hs.done == 2) {
-        res->status = PSK_BREAKDOWN;
-        res->exit = PSK_EXIT_DOT_BREAKDOWN;
-        res->success = 0;
-        res->iters = hs.iters;
-        res->resid = NAN;
-        result_msg(res, hs.brk_kind == 1   ? "breakdown dot(rhat,v)==0"
-                        : hs.brk_kind == 2 ? "breakdown dot(t,t)==0"
-                        : hs.brk_kind == 3 ? "breakdown omega==0"
-                                           : "breakdown dot(rhat,r)==0");
-    } else {   // maxiter reached: handleMaxiter(maxiter - 1, ...), as psk_pcg
-        res->status = PSK_MAXITER;
-        res->exit = PSK_EXIT_MAXITER;
-        res->success = 0;
-        res->iters = maxiter > 0 ? maxiter - 1 : 0;
-        res->resid = hs.rec;
-        result_msg(res, "failure to converge");
-    }
-    if (nh > maxiter) nh = maxiter;
-    res->hist_len = nh;
-    if (hist && nh > 0) PSK_HIP(hipMemcpy(hist, r.w.hist, (size_t)nh * 8, hipMemcpyDeviceToHost));
-    PSK_TRY(from_device_vec(r.w.x, loc, r.n, xout, r.s));
-    PSK_HIP(hipStreamSynchronize(r.s));
-    return PSK_OK;
+    const char *brk = hs.brk_kind == 1   ? "breakdown dot(rhat,v)==0"
+                      : hs.brk_kind == 2 ? "breakdown dot(t,t)==0"
+                      : hs.brk_kind == 3 ? "breakdown omega==0"
+                                         : "breakdown dot(rhat,r)==0";
+    result_outcome({hs.zero_b, hs.done, hs.by_tol, hs.iters + 1, hs.iters, hs.rec, brk}, r.ctl->maxiter, res);
+    if (bicg_tol_exit(hs)) result_true_resid("BiCGStab", std::sqrt(true_sq), hs.tauNormB, r.ctl->tau, hs.rec, true, res);
+    return result_copy_out(r, hs.zero_b ? 0 : hs.nhist, r.w.hist, r.w.x, res, hist, xout, loc);
 }
 
 // the phases in order; the caller drains the stream when one fails
@@ -545,13 +480,7 @@ static int bicg_solve(BicgRun &r, const double *b, double *xout, psk_result *res
     bool run;
     PSK_TRY(bicg_init(r, poll, b, loc, &run));
     int64_t launched = 0;
-    for (int64_t k = 0; run && k < r.ctl->maxiter; ++k) {
-        bool stop;
-        PSK_TRY(poll.step<2>(k, r.C, r.s, &stop));
-        if (stop) break;
-        PSK_TRY(bicg_iteration(r, k));
-        launched = k + 1;
-    }
+    if (run) PSK_TRY(poll_loop<2>(poll, r, r.ctl->maxiter, &launched, [&](int64_t k) { return bicg_iteration(r, k); }));
     BicgState hs;
     double true_sq;
     PSK_TRY(bicg_finish(r, &hs, &true_sq, res));
@@ -564,33 +493,12 @@ using namespace psk;
 
 extern "C" int psk_bicgstab(const psk_csr *Ac, const psk_prec *M, const double *b, double *xout, const psk_ctl *ctl,
                             psk_result *res, double *hist, int32_t loc) {
-    if (!Ac || !b || !xout || !ctl || !res) return fail(PSK_ERR_ARG, "psk_bicgstab: NULL argument");
-    if (ctl->maxiter < 0) return fail(PSK_ERR_ARG, "psk_bicgstab: negative maxiter");
-    if (M && M->n != Ac->n) return fail(PSK_ERR_ARG, "psk_bicgstab: preconditioner size mismatch");
-    if (!Ac->comm && Ac->ncols != Ac->n) return fail(PSK_ERR_ARG, "psk_bicgstab: matrix must be square");
-    if (Ac->comm && Ac->comm->nranks > 1)
-        return fail(PSK_ERR_UNSUPPORTED, "psk_bicgstab: sharded BiCGStab not built (replicas only)");
     BicgRun r{};
-    r.A = const_cast<psk_csr *>(Ac);
-    r.M = M;
-    r.ctl = ctl;
-    PSK_TRY(ctx(&r.c));
-    std::lock_guard<std::mutex> solve_lock(r.c->solve_mu);
-    r.s = r.c->stream;
-    std::memset(res, 0, sizeof(*res));
-    r.n = Ac->n;
-    r.nv = r.n > 0 ? (r.n + kVecTile - 1) / kVecTile : 1;
-    if (r.nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_bicgstab: vector too long for a one-shot grid");
-    r.C = ctl->check_every > 0 ? ctl->check_every : (r.n >= (1 << 20) ? 2 : 16);
-    r.gen = prec_is_general(M);
-    r.dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
-    if (r.n == 0) {   // no rows: b = 0
-        result_trivial(res);
-        return PSK_OK;
-    }
-    const int rc = bicg_solve(r, b, xout, res, hist, loc);
-    // a solve that failed on the host side leaves no kernel of its own running behind the next solve
-    if (rc != PSK_OK) (void)hipStreamSynchronize(r.s);
-    return rc;
+    return solve_entry("psk_bicgstab", "BiCGStab", r, Ac, M, b, xout, ctl, res, 1, kVecTile, [&]() -> int {
+        if (r.n == 0) {   // no rows: b = 0
+            result_trivial(res);
+            return PSK_OK;
+        }
+        return bicg_solve(r, b, xout, res, hist, loc);
+    });
 }
-

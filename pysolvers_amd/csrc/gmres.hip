@@ -280,26 +280,15 @@ static void gm_layout(Carve &big, Carve &sm, int64_t n, int64_t maxiter, int64_t
     w.hv = sm.take<double>((size_t)(K + 2) * 8);    // K + 2 grid sums of a step (gm_mgs_kernel)
 }
 void gmres_layout_probe(int64_t n, int64_t maxiter, int64_t restart, bool gen, std::vector<int64_t> *log, int64_t *bytes) {
-    Carve big, sm;
-    big.log = sm.log = log;
     GmresWork w;
-    gm_layout(big, sm, n, maxiter, gm_basis(maxiter, restart), gen, w);
-    bytes[0] = (int64_t)big.off;
-    bytes[1] = (int64_t)sm.off;
+    const int64_t K = gm_basis(maxiter, restart);
+    layout_sizes([&](Carve &big, Carve &sm) { gm_layout(big, sm, n, maxiter, K, gen, w); }, 0, log, bytes);
 }
-// A->ws and A->ws_small carved by gm_layout; need[2]: the bytes of each the layout covers. grow: size the two
-// buffers first (a later solve then keeps them); otherwise PSK_ERR_ARG when either is smaller than the layout.
+// A->ws and A->ws_small carved by gm_layout; need[2]: the bytes of each the layout covers; grow: as workspace_carve
 static int gm_workspace(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool grow, GmresWork &w, int64_t *need) {
-    gmres_layout_probe(A->n, maxiter, restart, gen, nullptr, need);
-    if (grow) {
-        PSK_TRY(A->ws.ensure((size_t)need[0]));
-        PSK_TRY(A->ws_small.ensure((size_t)need[1]));
-    }
-    if (!A->ws.p || !A->ws_small.p || A->ws.bytes < (size_t)need[0] || A->ws_small.bytes < (size_t)need[1])
-        return fail(PSK_ERR_ARG, "gmres_work_view: the matrix's workspace is smaller than this layout");
-    Carve big{A->ws.as<char>()}, sm{A->ws_small.as<char>()};
-    gm_layout(big, sm, A->n, maxiter, gm_basis(maxiter, restart), gen, w);
-    return PSK_OK;
+    const int64_t K = gm_basis(maxiter, restart);
+    auto layout = [&](Carve &big, Carve &sm) { gm_layout(big, sm, A->n, maxiter, K, gen, w); };
+    return workspace_carve(A, 0, grow, layout, need);
 }
 // the regions psk_gmres(maxiter, restart, gen) carved on this matrix. Host code only (psk_lab_gmres_internals,
 // psk_lab_gmres_prefill).
@@ -330,18 +319,12 @@ int gmres_work_view(psk_csr *A, int64_t maxiter, int64_t restart, bool gen, bool
     return PSK_OK;
 }
 
-struct GmresRun {
-    psk_csr *A;
-    const psk_prec *M;
-    const psk_ctl *ctl;
-    Context *c;
-    hipStream_t s;
-    int64_t n, nv, K;        // nv: the one-shot grid of the MGS kernels; K: the basis of a full cycle
+// what the phases share. nv: the one-shot grid of the MGS kernels; gen: M^-1 q_k is materialised in w before the SpMV;
+// C = 1: a poll chunk is one step
+struct GmresRun : SolveRun {
+    int64_t K;               // the basis of a full cycle
     int gv, ld;              // gv: the grid of the cycle start; ld = K + 1, the leading dimension of H and R
-    bool gen;                // general (ILU) preconditioner: M^-1 q_k is materialised in w before the SpMV
-    const double *dinv;
     GmresWork w;
-    SolveKit *kit;
     int64_t it, spmvs;       // iterations completed before this cycle; SpMV launches enqueued
     bool hit_maxiter;
     GmresState hs;           // the device state as last read (gm_read_state)
@@ -453,19 +436,10 @@ static int gm_converged(GmresRun &r, psk_result *res) {
     const GmresState &hs = r.hs;
     res->iters = r.it + kc + 1;
     res->exit = hs.brk ? PSK_EXIT_ARNOLDI_BREAKDOWN : PSK_EXIT_TOLERANCE;
-    res->resid = hs.true_resid;
     res->resid_recursive = hs.rec;
-    if (hs.true_resid <= hs.tauNormB) {
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-    } else {
-        res->status = PSK_TRUE_RESID_FAIL;
-        res->success = 0;
-        std::snprintf(res->msg, sizeof(res->msg),
-                      "GMRES failure: true residual %12.5g did not meet tolerance tau=%12.5g. "
-                      "Recursive residual was %12.5g.",
-                      hs.true_resid, r.ctl->tau, hs.rec);
-    }
+    res->status = PSK_CONVERGED;
+    res->success = 1;
+    result_true_resid("GMRES", hs.true_resid, hs.tauNormB, r.ctl->tau, hs.rec, true, res);
     return PSK_OK;
 }
 
@@ -475,50 +449,24 @@ static int gm_cycle_end(GmresRun &r, int64_t Kc, psk_result *res) {
     r.it += Kc;
     if (r.it < r.ctl->maxiter) return PSK_OK;
     // maxiter reached (reference: NameError at :180) -> handleMaxiter(k, x, |g|, ...)
+    // without fail_on_maxiter a stop that the tolerance did not make, at the same iteration number
     r.hit_maxiter = true;
-    res->exit = PSK_EXIT_MAXITER;
-    res->iters = r.ctl->maxiter > 0 ? r.ctl->maxiter - 1 : 0;
-    res->resid = r.hs.rec;
     res->resid_recursive = r.hs.rec;
-    if (r.ctl->fail_on_maxiter) {
-        res->status = PSK_MAXITER;
-        res->success = 0;
-        result_msg(res, "failure to converge");
-    } else {
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-    }
+    const int64_t maxiter = r.ctl->maxiter;
+    result_outcome({0, r.ctl->fail_on_maxiter ? 0 : 1, 0, maxiter_iters(maxiter), 0, r.hs.rec, nullptr}, maxiter, res);
     return PSK_OK;
 }
 
 // behind the last cycle: the checks of the in-launch reductions, loop_ms, norm_b, the b = 0 result, the history, x
 static int gm_report(GmresRun &r, psk_result *res, double *hist, double *xout, int32_t loc) {
     const GmresState &hs = r.hs;
-    const int64_t maxiter = r.ctl->maxiter;
-    PSK_HIP(hipEventRecord(r.kit->ev1, r.s));
-    PSK_HIP(hipStreamSynchronize(r.s));
-    // an expired in-launch reduction wait (MGS / normalisation / SpMV dots) poisons h with NaN; report it
-    // as the error it is rather than as a numerical non-convergence (and never to a later solve)
-    PSK_TRY(gridsum_check(r.c));
-    if (r.gen) PSK_TRY(prec_check_error(r.M, r.s));
-    res->loop_ms = loop_ms(r.kit);
+    PSK_TRY(solve_finish(r, res));   // the MGS / normalisation / SpMV dots are in-launch reductions
     res->norm_b = hs.normB;
     res->spmv_launches = r.spmvs;
-    if (hs.zero_b) {   // b = 0: handleConvergence(0, zeros, 0, 0)
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-        res->iters = 1;
-        res->resid = 0.0;
-        res->exit = PSK_EXIT_NONE;
-    }
+    if (hs.zero_b) result_trivial(res);   // no step ran and res is as the entry point zeroed it (resid = 0)
     // every step reported one residual (reportIter, :155): iters + 1 entries at maxiter (k = maxiter - 1)
-    const int64_t nh = res->iters + (r.hit_maxiter ? 1 : 0);
-    const int64_t nhc = hs.zero_b ? 0 : (nh < maxiter ? nh : maxiter);
-    res->hist_len = nhc;
-    if (hist && nhc > 0) PSK_HIP(hipMemcpy(hist, r.w.dhist, (size_t)nhc * 8, hipMemcpyDeviceToHost));
-    PSK_TRY(from_device_vec(r.w.x, loc, r.n, xout, r.s));
-    PSK_HIP(hipStreamSynchronize(r.s));
-    return PSK_OK;
+    const int64_t nh = hs.zero_b ? 0 : res->iters + (r.hit_maxiter ? 1 : 0);
+    return result_copy_out(r, nh, r.w.dhist, r.w.x, res, hist, xout, loc);
 }
 
 static int gm_solve(GmresRun &r, const double *b, double *xout, psk_result *res, double *hist, int32_t loc) {
@@ -547,12 +495,8 @@ static int gm_solve(GmresRun &r, const double *b, double *xout, psk_result *res,
         // Step numbers and stamps count from the cycle's start. A stamp ends the solve, so none is left over from an
         // earlier cycle, and the stream is drained between cycles: step k is not enqueued iff `done` was raised at
         // a step <= k - 3 of this cycle.
-        for (int64_t k = 0; k < Kc; ++k) {
-            bool stop;
-            PSK_TRY(poll.step<2>(k, 1, s, &stop));
-            if (stop) break;
-            PSK_TRY(gm_step(r, k));
-        }
+        int64_t steps = 0;   // not needed: the state says where the cycle ended
+        PSK_TRY(poll_loop<2>(poll, r, Kc, &steps, [&](int64_t k) { return gm_step(r, k); }));
         PSK_TRY(gm_read_state(r));
         if (r.hs.done) {
             PSK_TRY(gm_converged(r, res));
@@ -570,35 +514,19 @@ using namespace psk;
 
 extern "C" int psk_gmres(const psk_csr *Ac, const psk_prec *M, const double *b, double *xout,
                          const psk_ctl *ctl, psk_result *res, double *hist, int32_t loc) {
-    if (!Ac || !b || !xout || !ctl || !res) return fail(PSK_ERR_ARG, "psk_gmres: NULL argument");
-    if (ctl->maxiter < 0 || ctl->restart < 0) return fail(PSK_ERR_ARG, "psk_gmres: negative maxiter/restart");
-    if (M && M->n != Ac->n) return fail(PSK_ERR_ARG, "psk_gmres: preconditioner size mismatch");
-    if (!Ac->comm && Ac->ncols != Ac->n) return fail(PSK_ERR_ARG, "psk_gmres: matrix must be square");
-    if (Ac->comm && Ac->comm->nranks > 1)
-        return fail(PSK_ERR_UNSUPPORTED, "psk_gmres: sharded GMRES not built (replicas only)");
+    // restart is this entry point's own argument; its refusal names both, so it is made here for both
+    if (ctl && (ctl->maxiter < 0 || ctl->restart < 0)) return fail(PSK_ERR_ARG, "psk_gmres: negative maxiter/restart");
     GmresRun r{};
-    r.A = const_cast<psk_csr *>(Ac);
-    r.M = M;
-    r.ctl = ctl;
-    PSK_TRY(ctx(&r.c));
-    std::lock_guard<std::mutex> solve_lock(r.c->solve_mu);
-    r.s = r.c->stream;
-    std::memset(res, 0, sizeof(*res));
-    r.n = Ac->n;
-    r.K = gm_basis(ctl->maxiter, ctl->restart);
-    r.ld = (int)(r.K + 1);
-    r.gv = grid_for_rows(r.c, r.n, kVecTile);
-    r.nv = r.n > 0 ? (r.n + kVecTile - 1) / kVecTile : 1;
-    if (r.nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_gmres: vector too long for a one-shot grid");
-    r.gen = prec_is_general(M);
-    r.dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
-    PSK_TRY(gm_fits_hbm(r));
-    if (r.n == 0) {   // no rows: b = 0
-        result_trivial(res);
-        return PSK_OK;
-    }
-    const int rc = gm_solve(r, b, xout, res, hist, loc);
-    // a solve that failed on the host side leaves no kernel of its own running behind the next solve
-    if (rc != PSK_OK) (void)hipStreamSynchronize(r.s);
-    return rc;
+    return solve_entry("psk_gmres", "GMRES", r, Ac, M, b, xout, ctl, res, 1, kVecTile, [&]() -> int {
+        r.K = gm_basis(ctl->maxiter, ctl->restart);
+        r.ld = (int)(r.K + 1);
+        r.gv = grid_for_rows(r.c, r.n, kVecTile);
+        r.C = 1;
+        PSK_TRY(gm_fits_hbm(r));
+        if (r.n == 0) {   // no rows: b = 0
+            result_trivial(res);
+            return PSK_OK;
+        }
+        return gm_solve(r, b, xout, res, hist, loc);
+    });
 }

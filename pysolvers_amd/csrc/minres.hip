@@ -409,38 +409,19 @@ static void minres_layout(Carve &big, Carve &sm, int64_t n, int64_t maxiter, boo
     w.hist = sm.take<double>((size_t)(maxiter + 1) * 8);
 }
 void minres_layout_probe(int64_t n, int64_t maxiter, bool gen, std::vector<int64_t> *log, int64_t *bytes) {
-    Carve big, sm;
-    big.log = sm.log = log;
     MinresWork w;
-    minres_layout(big, sm, n, maxiter, gen, w);
-    bytes[0] = big.off > 0 ? (int64_t)big.off : 256;
-    bytes[1] = (int64_t)sm.off;
+    layout_sizes([&](Carve &big, Carve &sm) { minres_layout(big, sm, n, maxiter, gen, w); }, kWsFloor, log, bytes);
 }
 
 // what the phases of one solve share
-struct MinresRun {
-    psk_csr *A;
-    const psk_prec *M;
-    const psk_ctl *ctl;
-    Context *c;
-    SolveKit *kit;
-    hipStream_t s;
-    int64_t n, nv;
-    int C;           // iterations per poll chunk
-    bool gen;
-    const double *dinv;
+struct MinresRun : SolveRun {
     MinresWork w;
     GridSum gsA, gsB;   // alfa (U1), beta^2 (U2 or the general path's dot)
 };
 
 static int minres_workspace(MinresRun &r) {
-    int64_t need[2];
-    minres_layout_probe(r.n, r.ctl->maxiter, r.gen, nullptr, need);
-    PSK_TRY(r.A->ws.ensure((size_t)need[0]));
-    PSK_TRY(r.A->ws_small.ensure((size_t)need[1]));
-    Carve big{r.A->ws.as<char>()}, sm{r.A->ws_small.as<char>()};
-    minres_layout(big, sm, r.n, r.ctl->maxiter, r.gen, r.w);
-    return PSK_OK;
+    auto layout = [&](Carve &big, Carve &sm) { minres_layout(big, sm, r.n, r.ctl->maxiter, r.gen, r.w); };
+    return workspace_carve(r.A, kWsFloor, true, layout, nullptr);
 }
 
 // the vectors iteration k reads and writes: r1_0 = r2_0 = b, r2_k = r[(k-1) % 2] and U2 writes r[k % 2], which held
@@ -544,13 +525,7 @@ static int minres_finish(MinresRun &r, MinresState *hs, double *true_sq, psk_res
         PSK_TRY(launch_spmv(r.A, kSpmvResid, w.x, w.y, nullptr, w.bv, w.sums + kMinresTrue, nullptr, s));
         PSK_HIP(hipMemcpyAsync(true_sq, w.sums + kMinresTrue, 8, hipMemcpyDeviceToHost, s));
     }
-    PSK_HIP(hipEventRecord(r.kit->ev1, s));
-    PSK_HIP(hipStreamSynchronize(s));
-    // an expired in-launch reduction wait poisons a sum with NaN; report it as the error it is
-    PSK_TRY(gridsum_check(r.c));
-    if (r.gen) PSK_TRY(prec_check_error(r.M, s));
-    res->loop_ms = loop_ms(r.kit);
-    return PSK_OK;
+    return solve_finish(r, res);
 }
 
 // SpMV launches of the loop that did their work (those enqueued behind `done` returned at once): `done` is only
@@ -563,55 +538,16 @@ static int64_t minres_spmv_count(const MinresState &hs, int64_t launched) {
 // The state hs of a finished loop that enqueued `launched` iterations, decoded into res; the history and x.
 static int minres_report(const MinresRun &r, const MinresState &hs, int64_t launched, double true_sq, psk_result *res,
                          double *hist, double *xout, int32_t loc) {
-    const int64_t maxiter = r.ctl->maxiter;
     res->norm_b = hs.normB;
     res->spmv_launches = minres_spmv_count(hs, launched) + (minres_tol_exit(hs) ? 1 : 0);   // + the true residual's
     res->resid_recursive = hs.rec;
-    int64_t nh = hs.nhist;
-    if (hs.zero_b) {   // b = 0: x = 0 and resid = 0, as psk_pcg reports it
-        result_trivial(res);
-        nh = 0;
-    } else if (hs.done == 1) {
-        res->iters = hs.iters + 1;
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-        res->resid = hs.rec;
-        res->exit = hs.by_tol ? PSK_EXIT_TOLERANCE : PSK_EXIT_MAXITER;
-        if (minres_tol_exit(hs)) {
-            const double tr = std::sqrt(true_sq);
-            res->resid = tr;
-            // Under a preconditioner the test was made in the M^-1 norm, which is the solve's contract:
-            // ||r||_2 / ||b||_2 <= sqrt(cond(M)) tau, and the status stays converged.
-            if (!r.gen && !r.dinv && !(tr <= hs.tauNormB)) {
-                res->status = PSK_TRUE_RESID_FAIL;
-                res->success = 0;
-                std::snprintf(res->msg, sizeof(res->msg),
-                              "MINRES failure: true residual %12.5g did not meet tolerance tau=%12.5g. "
-                              "Recursive residual was %12.5g.",
-                              tr, r.ctl->tau, hs.rec);
-            }
-        }
-    } else if (hs.done == 2) {
-        res->status = PSK_BREAKDOWN;
-        res->exit = PSK_EXIT_DOT_BREAKDOWN;
-        res->success = 0;
-        res->iters = hs.iters;
-        res->resid = NAN;
-        result_msg(res, hs.brk_kind == 1 ? "preconditioner not positive definite" : "breakdown gamma==0");
-    } else {   // maxiter reached: handleMaxiter(maxiter - 1, ...), as psk_pcg
-        res->status = PSK_MAXITER;
-        res->exit = PSK_EXIT_MAXITER;
-        res->success = 0;
-        res->iters = maxiter > 0 ? maxiter - 1 : 0;
-        res->resid = hs.rec;
-        result_msg(res, "failure to converge");
-    }
-    if (nh > maxiter) nh = maxiter;
-    res->hist_len = nh;
-    if (hist && nh > 0) PSK_HIP(hipMemcpy(hist, r.w.hist, (size_t)nh * 8, hipMemcpyDeviceToHost));
-    PSK_TRY(from_device_vec(r.w.x, loc, r.n, xout, r.s));
-    PSK_HIP(hipStreamSynchronize(r.s));
-    return PSK_OK;
+    const char *brk = hs.brk_kind == 1 ? "preconditioner not positive definite" : "breakdown gamma==0";
+    result_outcome({hs.zero_b, hs.done, hs.by_tol, hs.iters + 1, hs.iters, hs.rec, brk}, r.ctl->maxiter, res);
+    // Under a preconditioner the test was made in the M^-1 norm, which is the solve's contract:
+    // ||r||_2 / ||b||_2 <= sqrt(cond(M)) tau, and the status stays converged.
+    if (minres_tol_exit(hs))
+        result_true_resid("MINRES", std::sqrt(true_sq), hs.tauNormB, r.ctl->tau, hs.rec, !r.gen && !r.dinv, res);
+    return result_copy_out(r, hs.zero_b ? 0 : hs.nhist, r.w.hist, r.w.x, res, hist, xout, loc);
 }
 
 // the phases in order; the caller drains the stream when one fails
@@ -622,13 +558,7 @@ static int minres_solve(MinresRun &r, const double *b, double *xout, psk_result 
     bool run;
     PSK_TRY(minres_init(r, poll, b, loc, &run));
     int64_t launched = 0;
-    for (int64_t k = 0; run && k < r.ctl->maxiter; ++k) {
-        bool stop;
-        PSK_TRY(poll.step<2>(k, r.C, r.s, &stop));
-        if (stop) break;
-        PSK_TRY(minres_iteration(r, k));
-        launched = k + 1;
-    }
+    if (run) PSK_TRY(poll_loop<2>(poll, r, r.ctl->maxiter, &launched, [&](int64_t k) { return minres_iteration(r, k); }));
     MinresState hs;
     double true_sq;
     PSK_TRY(minres_finish(r, &hs, &true_sq, res));
@@ -641,32 +571,12 @@ using namespace psk;
 
 extern "C" int psk_minres(const psk_csr *Ac, const psk_prec *M, const double *b, double *xout, const psk_ctl *ctl,
                           psk_result *res, double *hist, int32_t loc) {
-    if (!Ac || !b || !xout || !ctl || !res) return fail(PSK_ERR_ARG, "psk_minres: NULL argument");
-    if (ctl->maxiter < 0) return fail(PSK_ERR_ARG, "psk_minres: negative maxiter");
-    if (M && M->n != Ac->n) return fail(PSK_ERR_ARG, "psk_minres: preconditioner size mismatch");
-    if (!Ac->comm && Ac->ncols != Ac->n) return fail(PSK_ERR_ARG, "psk_minres: matrix must be square");
-    if (Ac->comm && Ac->comm->nranks > 1)
-        return fail(PSK_ERR_UNSUPPORTED, "psk_minres: sharded MINRES not built (replicas only)");
     MinresRun r{};
-    r.A = const_cast<psk_csr *>(Ac);
-    r.M = M;
-    r.ctl = ctl;
-    PSK_TRY(ctx(&r.c));
-    std::lock_guard<std::mutex> solve_lock(r.c->solve_mu);
-    r.s = r.c->stream;
-    std::memset(res, 0, sizeof(*res));
-    r.n = Ac->n;
-    r.nv = r.n > 0 ? (r.n + kVecTile - 1) / kVecTile : 1;
-    if (r.nv > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_minres: vector too long for a one-shot grid");
-    r.C = ctl->check_every > 0 ? ctl->check_every : (r.n >= (1 << 20) ? 2 : 16);
-    r.gen = prec_is_general(M);
-    r.dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
-    if (r.n == 0) {   // no rows: b = 0
-        result_trivial(res);
-        return PSK_OK;
-    }
-    const int rc = minres_solve(r, b, xout, res, hist, loc);
-    // a solve that failed on the host side leaves no kernel of its own running behind the next solve
-    if (rc != PSK_OK) (void)hipStreamSynchronize(r.s);
-    return rc;
+    return solve_entry("psk_minres", "MINRES", r, Ac, M, b, xout, ctl, res, 1, kVecTile, [&]() -> int {
+        if (r.n == 0) {   // no rows: b = 0
+            result_trivial(res);
+            return PSK_OK;
+        }
+        return minres_solve(r, b, xout, res, hist, loc);
+    });
 }

@@ -428,25 +428,21 @@ static void pcgm_layout(Carve &big, Carve &sm, int64_t n, int64_t maxiter, int n
     w.paps = sm.take<double>(it);
 }
 void pcg_multi_layout_probe(int64_t n, int64_t maxiter, int nrhs, std::vector<int64_t> *log, int64_t *bytes) {
-    Carve big, sm;
-    big.log = sm.log = log;
     PcgMultiWork w;
-    pcgm_layout(big, sm, n, maxiter, nrhs, w);
-    bytes[0] = big.off > 0 ? (int64_t)big.off : 256;
-    bytes[1] = (int64_t)sm.off;
+    layout_sizes([&](Carve &big, Carve &sm) { pcgm_layout(big, sm, n, maxiter, nrhs, w); }, kWsFloor, log, bytes);
+}
+// A->ws and A->ws_small carved by pcgm_layout; grow: as workspace_carve
+static int pcgm_workspace(psk_csr *A, int64_t maxiter, int nrhs, bool grow, PcgMultiWork &w) {
+    auto layout = [&](Carve &big, Carve &sm) { pcgm_layout(big, sm, A->n, maxiter, nrhs, w); };
+    return workspace_carve(A, kWsFloor, grow, layout, nullptr);
 }
 
 // psk_pcg_multi's workspace as the lab library reads it after a solve
 int pcg_multi_work_view(psk_csr *A, int64_t maxiter, int nrhs, PcgMultiView *v) {
     if (nrhs < 1 || nrhs > kMultiMax || maxiter < 0) return fail(PSK_ERR_ARG, "pcg_multi_work_view: bad arguments");
-    int64_t need[2];
-    pcg_multi_layout_probe(A->n, maxiter, nrhs, nullptr, need);
-    if (A->ws.bytes < (size_t)need[0] || A->ws_small.bytes < (size_t)need[1])
-        return fail(PSK_ERR_ARG, "pcg_multi_work_view: the matrix's workspace is smaller than that solve's");
-    Carve big{A->ws.as<char>()}, sm{A->ws_small.as<char>()};
     PcgMultiWork w;
-    pcgm_layout(big, sm, A->n, maxiter, nrhs, w);
-    *v = PcgMultiView{A->n, pcgm_kp(nrhs), maxiter + 1, w.x, w.r, w.p, w.Ap, w.alphas, w.udrs, w.paps, w.st};
+    PSK_TRY(pcgm_workspace(A, maxiter, nrhs, false, w));
+    *v =PcgMultiView{A->n, pcgm_kp(nrhs), maxiter + 1, w.x, w.r, w.p, w.Ap, w.alphas, w.udrs, w.paps, w.st};
     return PSK_OK;
 }
 void pcg_multi_col_state(const void *state, int j, double *out) {
@@ -458,15 +454,9 @@ void pcg_multi_col_state(const void *state, int j, double *out) {
 size_t pcg_multi_state_bytes() { return sizeof(PcgMultiState); }
 
 // what the phases of one solve share
-struct PcgMultiRun {
-    psk_csr *A;
-    const psk_ctl *ctl;
-    Context *c;
-    SolveKit *kit;
-    hipStream_t s;
-    int64_t n, nv, nwg;
-    int nrhs, kp, C;
-    const double *dinv;
+struct PcgMultiRun : SolveRun {
+    int64_t nwg;   // the grid of the SpMM: tiles of A->tile_rows rows
+    int nrhs, kp;
     PcgMultiWork w;
     GridSum gsS, gsU;
     // ctl->time_kernels = T > 0: every T-th S launch between two events of the kit's ring
@@ -483,16 +473,6 @@ template <class F> static void pcgm_dispatch(int kp, bool jac, F &&f) {
         if (jac) f(std::integral_constant<int, 4>{}, std::true_type{});
         else f(std::integral_constant<int, 4>{}, std::false_type{});
     }
-}
-
-static int pcgm_workspace(PcgMultiRun &r) {
-    int64_t need[2];
-    pcg_multi_layout_probe(r.n, r.ctl->maxiter, r.nrhs, nullptr, need);
-    PSK_TRY(r.A->ws.ensure((size_t)need[0]));
-    PSK_TRY(r.A->ws_small.ensure((size_t)need[1]));
-    Carve big{r.A->ws.as<char>()}, sm{r.A->ws_small.as<char>()};
-    pcgm_layout(big, sm, r.n, r.ctl->maxiter, r.nrhs, r.w);
-    return PSK_OK;
 }
 
 // everything in front of the loop: the gridsums, the state, B and the init launch
@@ -589,51 +569,20 @@ static int pcgm_report(const PcgMultiRun &r, const PcgMultiState &hs, int j, psk
     const int64_t maxiter = r.ctl->maxiter;
     res->norm_b = c.normB;
     res->resid_recursive = c.rec;
-    if (c.zero_b) {   // b = 0: x = 0 and resid = 0
-        result_trivial(res);
-    } else if (c.done == 1) {
-        res->status = PSK_CONVERGED;
-        res->success = 1;
-        res->iters = c.iters;
-        res->resid = c.rec;
-        res->exit = c.by_tol ? PSK_EXIT_TOLERANCE : PSK_EXIT_MAXITER;
-    } else if (c.done == 2) {
-        res->status = PSK_BREAKDOWN;
-        res->exit = PSK_EXIT_DOT_BREAKDOWN;
-        res->success = 0;
-        res->iters = c.iters;
-        res->resid = NAN;
-        result_msg(res, c.brk_kind == 1 ? "breakdown dot(u,r)==0" : "breakdown dot(p, Ap)==0");
-    } else {   // maxiter reached: handleMaxiter(maxiter - 1, ...), as psk_pcg
-        res->status = PSK_MAXITER;
-        res->exit = PSK_EXIT_MAXITER;
-        res->success = 0;
-        res->iters = maxiter > 0 ? maxiter - 1 : 0;
-        res->resid = c.rec;
-        result_msg(res, "failure to converge");
-    }
-    const int64_t nh = c.nhist < maxiter ? c.nhist : maxiter;
-    res->hist_len = nh;
-    if (hist && nh > 0)
-        PSK_HIP(hipMemcpy(hist + (size_t)j * (size_t)maxiter, r.w.hist + (size_t)j * (size_t)maxiter, (size_t)nh * 8,
-                          hipMemcpyDeviceToHost));
-    return PSK_OK;
+    const char *brk = c.brk_kind == 1 ? "breakdown dot(u,r)==0" : "breakdown dot(p, Ap)==0";
+    result_outcome({c.zero_b, c.done, c.by_tol, c.iters, c.iters, c.rec, brk}, maxiter, res);
+    const size_t at = (size_t)j * (size_t)maxiter;   // column j's history, maxiter entries apart on both sides
+    return result_history(c.nhist, maxiter, r.w.hist + at, res, hist ? hist + at : nullptr);
 }
 
 // the phases in order; the caller drains the stream when one fails
 static int pcgm_solve(PcgMultiRun &r, const double *B, double *X, psk_result *res, double *hist, int32_t loc) {
-    PSK_TRY(pcgm_workspace(r));
+    PSK_TRY(pcgm_workspace(r.A, r.ctl->maxiter, r.nrhs, true, r.w));
     PSK_TRY(solve_kit(r.c, r.ctl->time_kernels > 0, &r.kit));
     StampPoll poll(r.kit);   // the host-mapped done stamp the finishers write (pcgm_stop)
     PSK_TRY(pcgm_init(r, poll, B, loc));
     int64_t launched = 0;
-    for (int64_t k = 0; k < r.ctl->maxiter; ++k) {
-        bool stop;
-        PSK_TRY(poll.step<2>(k, r.C, r.s, &stop));
-        if (stop) break;
-        PSK_TRY(pcgm_iteration(r, k));
-        launched = k + 1;
-    }
+    PSK_TRY(poll_loop<2>(poll, r, r.ctl->maxiter, &launched, [&](int64_t k) { return pcgm_iteration(r, k); }));
     PcgMultiState hs;
     double loop = 0.0;
     PSK_TRY(pcgm_finish(r, &hs, X, loc, &loop));
@@ -655,12 +604,12 @@ using namespace psk;
 
 extern "C" int psk_pcg_multi(const psk_csr *Ac, const psk_prec *M, int32_t nrhs, const double *B, double *X,
                              const psk_ctl *ctl, psk_result *res, double *hist, int32_t loc) {
+    // what only this entry point refuses, and its own wording for a sharded matrix, in front of solve_entry (which
+    // tests the pointers again): nrhs sizes the results it zeroes, and these read the handles
     if (!Ac || !B || !X || !ctl || !res) return fail(PSK_ERR_ARG, "psk_pcg_multi: NULL argument");
     if (nrhs < 1 || nrhs > PSK_PCG_MULTI_MAX)
         return fail(PSK_ERR_ARG, "psk_pcg_multi: nrhs must be 1 .. " + std::to_string(PSK_PCG_MULTI_MAX));
     if (X == B) return fail(PSK_ERR_ARG, "psk_pcg_multi: X must not alias B");
-    if (ctl->maxiter < 0) return fail(PSK_ERR_ARG, "psk_pcg_multi: negative maxiter");
-    if (M && M->n != Ac->n) return fail(PSK_ERR_ARG, "psk_pcg_multi: preconditioner size mismatch");
     if (Ac->comm && Ac->comm->nranks > 1)
         return fail(PSK_ERR_UNSUPPORTED, "psk_pcg_multi: sharded multi-column PCG not built");
     if (Ac->ncols != Ac->n) return fail(PSK_ERR_ARG, "psk_pcg_multi: matrix must be square");
@@ -671,27 +620,16 @@ extern "C" int psk_pcg_multi(const psk_csr *Ac, const psk_prec *M, int32_t nrhs,
     if (Ac->n > 0 && (!Ac->rowptr || !Ac->colidx || !Ac->vals))
         return fail(PSK_ERR_UNSUPPORTED, "psk_pcg_multi: the matrix does not hold its CSR arrays");
     PcgMultiRun r{};
-    r.A = const_cast<psk_csr *>(Ac);
-    r.ctl = ctl;
-    PSK_TRY(ctx(&r.c));
-    std::lock_guard<std::mutex> solve_lock(r.c->solve_mu);
-    r.s = r.c->stream;
-    std::memset(res, 0, sizeof(*res) * (size_t)nrhs);
-    r.n = Ac->n;
-    r.nrhs = nrhs;
-    r.kp = pcgm_kp(nrhs);
-    r.nv = r.n > 0 ? (r.n + kMultiTile - 1) / kMultiTile : 1;
-    r.nwg = r.n > 0 ? (r.n + Ac->tile_rows - 1) / Ac->tile_rows : 1;
-    if (r.nwg > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_pcg_multi: matrix too long for a one-shot grid");
-    r.C = ctl->check_every > 0 ? ctl->check_every : (r.n >= (1 << 20) ? 2 : 16);
-    r.dinv = (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
-    for (int i = 0; i < kTimedSlots; ++i) r.tk[i] = -1;
-    if (r.n == 0) {   // no rows: every b = 0
-        for (int j = 0; j < nrhs; ++j) result_trivial(&res[j]);
-        return PSK_OK;
-    }
-    const int rc = pcgm_solve(r, B, X, res, hist, loc);
-    // a solve that failed on the host side leaves no kernel of its own running behind the next solve
-    if (rc != PSK_OK) (void)hipStreamSynchronize(r.s);
-    return rc;
+    return solve_entry("psk_pcg_multi", "multi-column PCG", r, Ac, M, B, X, ctl, res, nrhs, kMultiTile, [&]() -> int {
+        r.nrhs = nrhs;
+        r.kp = pcgm_kp(nrhs);
+        r.nwg = r.n > 0 ? (r.n + Ac->tile_rows - 1) / Ac->tile_rows : 1;
+        if (r.nwg > INT32_MAX) return fail(PSK_ERR_UNSUPPORTED, "psk_pcg_multi: matrix too long for a one-shot grid");
+        for (int i = 0; i < kTimedSlots; ++i) r.tk[i] = -1;
+        if (r.n == 0) {   // no rows: every b = 0
+            for (int j = 0; j < nrhs; ++j) result_trivial(&res[j]);
+            return PSK_OK;
+        }
+        return pcgm_solve(r, B, X, res, hist, loc);
+    });
 }

@@ -954,6 +954,10 @@ inline bool prec_is_general(const psk_prec *M) {
     return M && (M->kind == PSK_PREC_ILU || M->kind == PSK_PREC_AMG || M->kind == PSK_PREC_DENSE ||
                  M->kind == PSK_PREC_CHEBYSHEV || M->kind == PSK_PREC_FSAI || M->kind == PSK_PREC_MCGS);
 }
+// Jacobi's DInv, which the drivers fold into their own kernels (null for every other kind)
+inline const double *prec_jacobi_dinv(const psk_prec *M) {
+    return (M && M->kind == PSK_PREC_JACOBI) ? M->dinv : nullptr;
+}
 // reports a bounded-spin timeout of any triangular solve inside M (syncs the stream)
 int prec_check_error(const psk_prec *M, hipStream_t s);
 int tile_rows_for(int64_t n, int64_t nnz);
