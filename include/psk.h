@@ -525,6 +525,46 @@ int psk_gmres(const psk_csr *A, const psk_prec *M, const double *b, double *x, c
  * PSK_ERR_UNSUPPORTED. */
 int psk_bicgstab(const psk_csr *A, const psk_prec *M, const double *b, double *x, const psk_ctl *ctl,
                  psk_result *res, double *hist, int32_t loc);
+/* Right-preconditioned IDR(s) (Sonneveld and van Gijzen) for nonsymmetric A (no reference counterpart): a fixed
+ * footprint of 2s + 5 vectors (2s + 6 with Jacobi, 2s + 7 with a general preconditioner; the shadow space is
+ * regenerated from a hash, never stored), ONE SpMV and one
+ * preconditioner apply per step, 1 <= s <= PSK_IDRS_MAX_S (ctl->restart is ignored). The biorthogonal variant, each new
+ * direction made orthogonal from a single s-wide dot product. One STEP is one SpMV: hist gets one entry per step, and
+ * iters, maxiter and hist_len count steps. x0 = 0, every elementwise operation rounded once:
+ *   P[i][j] = double(splitmix64(i*s + j) >> 11) * 2^-52 - 1.0, with splitmix64(t): z = t + 0x9E3779B97F4A7C15;
+ *     z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB; z ^ z>>31 (mod 2^64): exact in
+ *     f64, the same on every run, not orthonormalised
+ *   x = 0; r = b; normB = sqrt(b.b) (or ctl->norm_b); thr = tau*normB; G = U = 0 (n x s); Mm = I_s; om = 1; j = 0
+ *   cycle:
+ *     f_i = p_i.r, i = 0..s-1
+ *     for k = 0..s-1:
+ *       c_i, i = k..s-1:  t = f_i;  t = t - Mm[i][l]*c_l, l = k..i-1;  c_i = t / Mm[i][i]
+ *       v = r;  v = v - c_i*g_i, i = k..s-1;  v = M^-1 v;  u = om*v;  u = u + c_i*u_i, i = k..s-1
+ *       g = A u                                                                  (step j's SpMV)
+ *       q_i = p_i.g, i = 0..s-1
+ *       a_i, i = 0..k-1:  t = q_i;  t = t - Mm[i][l]*a_l, l = 0..i-1;  a_i = t / Mm[i][i]
+ *       g = g - a_i*g_i, u = u - a_i*u_i, i = 0..k-1;  g_k = g;  u_k = u
+ *       Mm[i][k], i = k..s-1:  t = q_i;  t = t - Mm[i][l]*a_l, l = 0..k-1;  Mm[i][k] = t
+ *       Mm[k][k] == 0: breakdown
+ *       beta = f_k / Mm[k][k];  r = r - beta*g;  x = x + beta*u;  hist[j] = sqrt(r.r);  stop test;  j++
+ *       f_i = f_i - beta*Mm[i][k], i = k+1..s-1
+ *     v = M^-1 r;  t = A v                                                       (step j's SpMV)
+ *     tt = t.t;  ts = t.r;  rr = the r.r of the previous step;  tt == 0 or ts == 0: breakdown
+ *     rho = ts / (sqrt(tt)*sqrt(rr));  om = ts/tt;  |rho| < 0.7: om = (om*0.7)/|rho|
+ *     x = x + om*v;  r = r - om*t;  hist[j] = sqrt(r.r);  stop test;  j++
+ *   stop test: hist[j] <= thr, or j == maxiter-1 with !fail_on_maxiter.
+ * Every dot product is a sum of products rounded one by one, one per row, in an order that depends on the tile and
+ * slot indices only: two identical calls give identical bits, whatever the SpMV layout of A.
+ * Stopping at step j: PSK_CONVERGED, iters = j+1, hist_len = j+1; on a tolerance exit (PSK_EXIT_TOLERANCE) resid = the
+ * true ||b - A x||, measured by one more SpMV, and resid_recursive the recursive one, PSK_TRUE_RESID_FAIL when the true
+ * one misses tau*||b|| (as psk_bicgstab). A breakdown at step j: PSK_BREAKDOWN, iters = j, hist_len = j
+ * (PSK_EXIT_DOT_BREAKDOWN), resid = NaN. maxiter reached: PSK_MAXITER, iters = maxiter-1. b = 0: as psk_pcg.
+ * ctl->norm_b as for psk_gmres. spmv_launches counts the SpMV launches that did their work: one per step, plus the
+ * true residual's. s outside 1..PSK_IDRS_MAX_S: PSK_ERR_ARG. A sharded A with more than one rank:
+ * PSK_ERR_UNSUPPORTED. */
+#define PSK_IDRS_MAX_S 8
+int psk_idrs(const psk_csr *A, const psk_prec *M, const double *b, double *x, const psk_ctl *ctl,
+             int32_t s, psk_result *res, double *hist, int32_t loc);
 /* Preconditioned MINRES for SYMMETRIC INDEFINITE A (no reference counterpart): Paige-Saunders MINRES in the
  * operation order of scipy.sparse.linalg.minres, with an SPD preconditioner M, x0 = 0, no shift; one SpMV, two dot
  * products and a fixed footprint per iteration (ctl->restart is ignored). Every elementwise operation rounded once:

@@ -36,7 +36,7 @@ class IterativeLinearSolverType(LinearSolverType):
 class IterativeLinearSolver(LinearSolver, IterativeSolver):
     """Solver base (IterativeLinearSolver.py:60-86) + the device driver."""
 
-    _entry = None          # "psk_pcg" / "psk_gmres" / "psk_bicgstab" / "psk_minres"
+    _entry = None          # "psk_pcg" / "psk_gmres" / "psk_bicgstab" / "psk_minres" / "psk_idrs"
     _method = "GMRES"      # the method's name in the true-residual failure text (GMRESSolver.py:167-174)
     # PCGSolver.solve prints 'prec frozen = ...' and 'building prec' on every solve with b != 0
     # (PCGSolver.py:91,93); PCGSolver sets this (class attribute: a driver may switch it off)
@@ -69,6 +69,10 @@ class IterativeLinearSolver(LinearSolver, IterativeSolver):
 
     def _restart(self):
         return 0
+
+    def _call_entry(self, A, M, b, x, ctl, res, hist, loc):
+        """The library call of one solve; a solver whose entry point takes more arguments overrides this."""
+        return getattr(N.lib, self._entry)(A, M, b, x, ctl, res, hist, loc)
 
     def _retests_true_residual(self, kind):
         """With a caller's norm: is a tolerance exit under a preconditioner of device kind `kind` re-tested
@@ -142,9 +146,8 @@ class IterativeLinearSolver(LinearSolver, IterativeSolver):
         res = N.PskResult()
         hist = np.zeros(max(maxiter, 1), dtype=np.float64)
         x, loc, bp = self._solve_vectors(b, n)
-        fn = getattr(N.lib, self._entry)
-        N.check(fn(dA.handle, ph, N.ptr(bp), N.ptr(x), ctypes.byref(ctl), ctypes.byref(res), N.ptr(hist), loc),
-                self._entry)
+        N.check(self._call_entry(dA.handle, ph, N.ptr(bp), N.ptr(x), ctypes.byref(ctl), ctypes.byref(res), N.ptr(hist),
+                                 loc), self._entry)
         if custom and res.exit in (N.PSK_EXIT_TOLERANCE, N.PSK_EXIT_ARNOLDI_BREAKDOWN) and \
                 self._retests_true_residual(kind):
             # GMRES / BiCGStab / MINRES stopped on the recursive residual: the true-residual test in the caller's norm

@@ -7,6 +7,7 @@ from .DeviceMatrix import DeviceCSR, DeviceVector, matmat, spmv
 from .DirectSolver import DefaultDirect, DefaultDirectSolver
 from .Distributed import Communicator, fd_laplacian_2d_sharded, halo_cols, shard_csr
 from .GMRESSolver import GMRES, GMRESSolver
+from .IDRsSolver import IDRs, IDRsSolver
 from .ILUTPreconditioner import (ILUTPreconditioner, LeftILUT, LeftILUTPreconditioner, RightILUT,
                                  RightILUTPreconditioner)
 from .ILU0Preconditioner import (ILU0Preconditioner, LeftILU0, LeftILU0Preconditioner, RightILU0,

@@ -5,7 +5,7 @@ there is no CPU fallback.
 """
 from . import Linear, Nonlinear, io
 from .IterativeSolver import CommonSolverArgs, IterativeSolver, NamedObject, SolveStatus
-from .Linear import (AMG, AMGVCycle, AMGVCycleSolver, BiCGStab, BiCGStabSolver, DefaultDirect, GMRES, MINRES, MINRESSolver, PCG, RightIC, GaussSeidelSmoother, JacobiSmoother, DeviceCSR, DeviceVector, GMRESSolver, IdentityPreconditioner,
+from .Linear import (AMG, AMGVCycle, AMGVCycleSolver, BiCGStab, BiCGStabSolver, DefaultDirect, GMRES, IDRs, IDRsSolver, MINRES, MINRESSolver, PCG, RightIC, GaussSeidelSmoother, JacobiSmoother, DeviceCSR, DeviceVector, GMRESSolver, IdentityPreconditioner,
                      IdentityPreconditionerType, IterativeLinearSolver, Jacobi, JacobiPreconditioner,
                      JacobiPreconditionerType, LeftILUT, PCGSolver, RightILUT, mvmult,
                      Chebyshev, ChebyshevPreconditioner, ChebyshevSmoother, LeftILU0, RightILU0,
@@ -13,7 +13,7 @@ from .Linear import (AMG, AMGVCycle, AMGVCycleSolver, BiCGStab, BiCGStabSolver, 
                      MulticolorGS, MulticolorGSPreconditioner, MulticolorGSPreconditionerType,
                      MulticolorGaussSeidelSmoother)
 
-__all__ = ["Nonlinear", "AMG", "AMGVCycle", "AMGVCycleSolver", "BiCGStab", "BiCGStabSolver", "MINRES", "MINRESSolver", "DefaultDirect", "RightIC", "GaussSeidelSmoother", "JacobiSmoother", "Linear", "CommonSolverArgs", "IterativeSolver", "NamedObject", "SolveStatus", "GMRES", "PCG",
+__all__ = ["Nonlinear", "AMG", "AMGVCycle", "AMGVCycleSolver", "BiCGStab", "BiCGStabSolver", "IDRs", "IDRsSolver", "MINRES", "MINRESSolver", "DefaultDirect", "RightIC", "GaussSeidelSmoother", "JacobiSmoother", "Linear", "CommonSolverArgs", "IterativeSolver", "NamedObject", "SolveStatus", "GMRES", "PCG",
            "GMRESSolver", "PCGSolver", "DeviceCSR", "DeviceVector", "IdentityPreconditioner",
            "IdentityPreconditionerType", "IterativeLinearSolver", "Jacobi", "JacobiPreconditioner",
            "JacobiPreconditionerType", "LeftILUT", "RightILUT", "mvmult",

@@ -30,6 +30,7 @@ PSK_MCGS_SYMMETRIC = 1      # psk_prec_create_mcgs flags: colours forward then b
 PSK_LAYOUT_CSR, PSK_LAYOUT_SLICED, PSK_LAYOUT_SLICED_WIDE, PSK_LAYOUT_SLICED_DICT, PSK_LAYOUT_DIAG = 0, 1, 2, 3, 4
 PSK_UNIQUE_ID_BYTES = 128
 PSK_PCG_MULTI_MAX = 4       # psk_pcg_multi: right-hand sides of one call
+PSK_IDRS_MAX_S = 8          # psk_idrs: the largest shadow-space dimension s
 PSK_SPGEMM_ROW_CAP = 1024   # psk_csr_matmat: products of one output row
 
 STATUS_NAMES = {PSK_CONVERGED: "converged", PSK_MAXITER: "maxiter", PSK_BREAKDOWN: "breakdown",
@@ -115,6 +116,7 @@ SIGNATURES = {
     "psk_gmres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_bicgstab": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_minres": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
+    "psk_idrs": (ctypes.c_int, [P, P, P, P, ctypes.POINTER(PskCtl), I32, ctypes.POINTER(PskResult), P, I32]),
     "psk_pcg_multi": (ctypes.c_int, [P, P, I32, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32]),
     "psk_vcycle": (ctypes.c_int, [P, P, P, ctypes.POINTER(PskCtl), ctypes.POINTER(PskResult), P, I32, I32]),
     "psk_comm_unique_id": (ctypes.c_int, [P]),
