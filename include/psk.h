@@ -41,6 +41,8 @@
  *                    MLHierarchy.py:283-322) on the device, same bits in the same stored order.
  *   psk_csr_ilu0, psk_prec_create_ilu0: ILU(0) factored on the device; no reference counterpart (the
  *                    reference's incomplete factors are SuperLU's).
+ *   psk_csr_iluk_pattern, psk_prec_create_iluk: level-of-fill ILU(k), the fill pattern built on the device; no
+ *                    reference counterpart.
  *   psk_prec_trisolve_sweeps: opt-in approximate triangular applies by Jacobi sweeps; no reference counterpart.
  *   psk_pcg_multi    several right-hand sides in one PCG loop, each column the recurrence of psk_pcg; no reference
  *                    counterpart (the reference solves one vector per call).
@@ -412,6 +414,38 @@ int psk_csr_ilu0(const psk_csr *A, psk_csr **F);
  * psk_prec_apply, psk_prec_info, psk_prec_trisolve_schedule and the solvers take it like any other. Errors as
  * psk_csr_ilu0; A is not borrowed. Replaces nothing in the reference. */
 int psk_prec_create_ilu0(const psk_csr *A, psk_prec **out);
+
+/* ---- level-of-fill ILU(k) on the device (iluk.hip) --------------------------------------------- */
+/* The ILU(k) pattern of a square A, built on the device. A has at most one stored entry per (row, column) and a
+ * stored diagonal entry in every row; its rows may be stored in any order; 0 <= k <= PSK_ILUK_MAX_LEVEL. With S = the
+ * copy of A whose rows are in ascending column order:
+ *   Levels. Every stored entry of A has level 0, explicit zeros included. Then, for i = 0 .. n-1: for each entry
+ *   (i, c) of row i with c < i, in ascending c (fill entries included as this same pass adds them), and for every entry
+ *   (c, j) of the finished row c with j > c: cand = lev(i,c) + lev(c,j) + 1; if cand <= k and (i, j) is absent or holds
+ *   a larger level, lev(i,j) = cand.
+ *   Pattern. Every entry with lev <= k.
+ * *P has that pattern with rows in ascending column order; it holds A's value where A stores the entry and +0.0 at
+ * a fill entry. *Lev (NULL: not wanted) has the same structure and the levels as doubles. Both end like
+ * psk_csr_create(..., PSK_DEVICE). The ILU(k) factor of A is, bit for bit, psk_csr_ilu0(*P) in the arithmetic stated
+ * above for psk_csr_ilu0; k = 0 gives S itself and therefore the bits of psk_csr_ilu0(A). The device algorithm
+ * (k rounds, each parallel over the rows; iluk.hip) gives exactly the pattern and levels of this sequential rule
+ * and does not depend on the launch geometry.
+ * PSK_ILUK_ROW_CAP = 512 is the longest row of *P the kernels hold (a row's new columns are collected in a hash set
+ * in LDS: 24 KiB per workgroup at this cap, six workgroups per CU; 1024 would halve that). The cap holds for k >= 1;
+ * k = 0 runs no round and takes rows of any length, as psk_csr_ilu0 does.
+ * PSK_ERR_ARG: A not square or empty, a column outside [0, n), a row without a stored diagonal entry, k out of range.
+ * PSK_ERR_UNSUPPORTED: a sharded A; a duplicate column within a row; for k >= 1 a filled row longer than PSK_ILUK_ROW_CAP
+ * (psk_last_error names the smallest such row); a result over the int32 nnz limit. *P and *Lev are written only on
+ * success. A is only read; nothing of it is borrowed. Replaces nothing in the reference. */
+#define PSK_ILUK_MAX_LEVEL 8
+#define PSK_ILUK_ROW_CAP 512
+int psk_csr_iluk_pattern(const psk_csr *A, int32_t k, psk_csr **P, psk_csr **Lev);
+/* The ILU(k) preconditioner of A: psk_csr_iluk_pattern, then psk_prec_create_ilu0 on the padded matrix — the numeric
+ * factorisation, the L / U split and the hand-off to the triangular-solve chain are those of ILU(0), unchanged. The
+ * result is a PSK_PREC_ILU: psk_prec_apply, psk_prec_info, psk_prec_trisolve_schedule, psk_prec_trisolve_sweeps and
+ * the solvers take it like any other. Errors as psk_csr_iluk_pattern, then as psk_csr_ilu0 (a zero or non-finite
+ * pivot on the padded pattern is reported in psk_csr_ilu0's words); A is not borrowed. */
+int psk_prec_create_iluk(const psk_csr *A, int32_t k, psk_prec **out);
 
 /* ---- factorized sparse approximate inverse on the device (fsai.hip) ---------------------------- */
 /* G = the FSAI factor of a square, symmetric, definite A on a prescribed pattern: a sparse lower-triangular

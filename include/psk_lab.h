@@ -159,6 +159,11 @@ int psk_lab_pcg_multi_internals(const psk_csr *A, int64_t maxiter, int32_t nrhs,
  * (planner and uploads; the last two are 0 after psk_csr_ilu0), then the level count and the lanes per row. Touches
  * no GPU. */
 int psk_lab_ilu0_timing(double *out);
+/* Measurement (tools/iluk_ab.py): the last psk_csr_iluk_pattern / psk_prec_create_iluk of this process. out[0..6] = ms
+ * of the symbolic phase (sort, rounds, padding; host wall time), the level k, the rounds that added entries, the
+ * rounds in which the 64-lane instance ran beside a narrower one, the lanes per row of the last round, nnz(A), nnz(P).
+ * The numeric and planner times of the same call are psk_lab_ilu0_timing's. Touches no GPU. */
+int psk_lab_iluk_timing(double *out);
 #ifdef __cplusplus
 }
 #endif

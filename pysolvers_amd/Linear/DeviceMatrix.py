@@ -185,6 +185,25 @@ class DeviceCSR:
         N.check(N.lib.psk_csr_ilu0(self._h, ctypes.byref(h)), "psk_csr_ilu0")
         return DeviceCSR._adopt(h, self.ncols)
 
+    def iluk_pattern(self, k, levels=False):
+        """This matrix padded with zeros onto its level-of-fill ILU(k) pattern, built on the device
+        (psk_csr_iluk_pattern; the level rule is stated in include/psk.h): a DeviceCSR P with rows in ascending column
+        order, this matrix's value where it stores the entry and +0.0 at a fill entry, so that ``P.ilu0()`` is the
+        ILU(k) factor. ``levels=True`` returns ``(P, Lev)``, Lev on the same structure with the levels as doubles.
+        ``k = 0`` gives the sorted copy of this matrix. ValueError for a k that is a bool, not an integer or outside
+        [0, 8] and for a sharded matrix; PskError with PSK_ERR_ARG for a missing diagonal entry, PSK_ERR_UNSUPPORTED
+        for a duplicate column or, for k >= 1, a filled row longer than PSK_ILUK_ROW_CAP = 512 (the message names the
+        row)."""
+        from .ILUKPreconditioner import check_level
+        k = check_level(k)
+        if self.comm is not None:
+            raise ValueError("ILU(k) of a sharded matrix is not supported")
+        hp, hl = ctypes.c_void_p(), ctypes.c_void_p()
+        N.check(N.lib.psk_csr_iluk_pattern(self._h, k, ctypes.byref(hp), ctypes.byref(hl) if levels else None),
+                "psk_csr_iluk_pattern")
+        P = DeviceCSR._adopt(hp, self.ncols)
+        return (P, DeviceCSR._adopt(hl, self.ncols)) if levels else P
+
     def fsai(self, pattern=None, flags=0):
         """``(G, sign)``: the factorized sparse approximate inverse of this symmetric definite matrix as a lower
         triangular DeviceCSR G ~ L^-1 (sign A = L L^T) on tril(pattern), formed on the device (psk_csr_fsai; the

@@ -12,6 +12,8 @@ from .ILUTPreconditioner import (ILUTPreconditioner, LeftILUT, LeftILUTPrecondit
                                  RightILUTPreconditioner)
 from .ILU0Preconditioner import (ILU0Preconditioner, LeftILU0, LeftILU0Preconditioner, RightILU0,
                                  RightILU0Preconditioner)
+from .ILUKPreconditioner import (ILUKPreconditioner, LeftILUK, LeftILUKPreconditioner, RightILUK,
+                                 RightILUKPreconditioner)
 from .ICPreconditioner import ICRightPreconditioner, RightIC
 from .IterativeLinearSolver import IterativeLinearSolver, IterativeLinearSolverType, mvmult
 from .LinearSolver import LinearSolver, LinearSolverType

@@ -9,6 +9,7 @@ from .Linear import (AMG, AMGVCycle, AMGVCycleSolver, BiCGStab, BiCGStabSolver, 
                      IdentityPreconditionerType, IterativeLinearSolver, Jacobi, JacobiPreconditioner,
                      JacobiPreconditionerType, LeftILUT, PCGSolver, RightILUT, mvmult,
                      Chebyshev, ChebyshevPreconditioner, ChebyshevSmoother, LeftILU0, RightILU0,
+                     LeftILUK, RightILUK, ILUKPreconditioner, LeftILUKPreconditioner, RightILUKPreconditioner,
                      FSAI, FSAIPreconditioner, FSAIPreconditionerType,
                      MulticolorGS, MulticolorGSPreconditioner, MulticolorGSPreconditionerType,
                      MulticolorGaussSeidelSmoother)
@@ -18,6 +19,7 @@ __all__ = ["Nonlinear", "AMG", "AMGVCycle", "AMGVCycleSolver", "BiCGStab", "BiCG
            "IdentityPreconditionerType", "IterativeLinearSolver", "Jacobi", "JacobiPreconditioner",
            "JacobiPreconditionerType", "LeftILUT", "RightILUT", "mvmult",
            "Chebyshev", "ChebyshevPreconditioner", "ChebyshevSmoother", "LeftILU0", "RightILU0",
+           "LeftILUK", "RightILUK", "ILUKPreconditioner", "LeftILUKPreconditioner", "RightILUKPreconditioner",
            "FSAI", "FSAIPreconditioner", "FSAIPreconditionerType",
            "MulticolorGS", "MulticolorGSPreconditioner", "MulticolorGSPreconditionerType",
            "MulticolorGaussSeidelSmoother"]

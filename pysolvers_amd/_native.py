@@ -106,6 +106,8 @@ SIGNATURES = {
     "psk_sa_prolongator": (ctypes.c_int, [P, P, I64, P, F64, I32, PP]),
     "psk_csr_ilu0": (ctypes.c_int, [P, PP]),
     "psk_prec_create_ilu0": (ctypes.c_int, [P, PP]),
+    "psk_csr_iluk_pattern": (ctypes.c_int, [P, I32, PP, PP]),
+    "psk_prec_create_iluk": (ctypes.c_int, [P, I32, PP]),
     "psk_csr_fsai": (ctypes.c_int, [P, P, I32, PP, ctypes.POINTER(I32)]),
     "psk_prec_create_fsai": (ctypes.c_int, [P, P, I32, PP]),
     "psk_prec_fsai_info": (ctypes.c_int, [P, ctypes.POINTER(I32), ctypes.POINTER(I64), ctypes.POINTER(I32)]),
@@ -164,6 +166,7 @@ LAB_SIGNATURES = {
     "psk_lab_pcg_prefill": (ctypes.c_int, [P, I64, I32, I32, I32]),
     "psk_lab_pcg_multi_internals": (ctypes.c_int, [P, I64, I32, P, P, P, P, P, P, P, P]),
     "psk_lab_ilu0_timing": (ctypes.c_int, [ctypes.POINTER(F64)]),
+    "psk_lab_iluk_timing": (ctypes.c_int, [ctypes.POINTER(F64)]),
 }
 _lab = None
 

@@ -215,6 +215,15 @@ extern "C" int psk_lab_cheby_ab(const psk_prec *M, const double *v, int32_t reps
     return psk::cheby_ab(M, v, reps, fused_ms, pieces_ms);
 }
 
+extern "C" int psk_lab_iluk_timing(double *out) {
+    if (!out) return psk::fail(PSK_ERR_ARG, "psk_lab_iluk_timing: NULL argument");
+    const psk::IlukTiming &t = psk::iluk_last_timing();
+    const double v[7] = {t.symbolic_ms, (double)t.level, (double)t.rounds, (double)t.wide_rounds, (double)t.width,
+                         (double)t.nnz_a, (double)t.nnz_p};
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
+    return PSK_OK;
+}
+
 extern "C" int psk_lab_ilu0_timing(double *out) {
     if (!out) return psk::fail(PSK_ERR_ARG, "psk_lab_ilu0_timing: NULL argument");
     const psk::Ilu0Timing &t = psk::ilu0_last_timing();

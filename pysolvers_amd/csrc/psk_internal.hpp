@@ -948,6 +948,16 @@ struct Ilu0Timing {
     int width = 0;
 };
 const Ilu0Timing &ilu0_last_timing();
+// the same for the symbolic phase of ILU(k) (iluk.hip): host wall time of psk_csr_iluk_pattern, the level asked for,
+// the rounds that added entries, the rounds that also ran the 64-lane instance, the lanes per row of the last round
+// and the entry counts before and after; the numeric and planner times of psk_prec_create_iluk are Ilu0Timing's
+struct IlukTiming {
+    double symbolic_ms = 0.0;
+    int32_t level = 0, rounds = 0, wide_rounds = 0;
+    int width = 0;
+    int64_t nnz_a = 0, nnz_p = 0;
+};
+const IlukTiming &iluk_last_timing();
 // preconditioners whose apply is not a single elementwise op (triangular solves, AMG, polynomials): the
 // Krylov drivers take their general path for these
 inline bool prec_is_general(const psk_prec *M) {
